@@ -4,6 +4,17 @@
     python bench.py --gpus N --steps K --warmup W            (N > 1: launches N ranks itself)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
+A plain run does what the headline figure needs and no more: set up, W warmup
+steps, K timed steps, the result line.  --full adds, after the timed steps,
+everything measured beside it: the streaming-copy rates of the roofline, the
+cpu_baseline legs with their bit-exact check of the GPU outputs, and for N > 1
+the gather-inclusive phase (config 4's --check runs that phase by itself).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy
+(float32; config 2: ``levels``; config 4: ``levels`` widened to int32, ``recon``
+and the TU maps; a fixed seeded sample of an array too large for its share of
+64 MB); the inputs are a function of the arguments alone, so two builds can be
+compared output for output.
+
 Launch: one process per GPU.  When WORLD_SIZE is unset and --gpus N > 1 the
 parent process starts `torch.distributed.run --nproc-per-node N` on this same
 script and exits with its status -- it never touches the GPU itself.  Under a
@@ -24,7 +35,7 @@ per 32x32 CTU, CTU-row bands per rank as above; every rank
 synthesises and holds only its bands plus the one source row above each band
 (all a TU reads, block.py:38-50; shard.Cfg4Layout) and reconstructs them.
 
-N > 1, both configs: after the compute-only phase, a gather-inclusive phase
+N > 1, both configs, --full: after the compute-only phase, a gather-inclusive phase
 runs the path's one exchange step -- an RCCL gather to rank 0 of every rank's
 whole output (config 2: all its int16 levels, 3.2 GB per rank at 128 frames,
 in --gather-chunk-frames pieces so rank 0's receive buffers stay bounded;
@@ -45,7 +56,7 @@ bytes per launch committed in profiles/pmc_traffic.json for this configuration
 (tools/pmc_traffic.py), else null.  Config 4: 2 B source + 4 B levels + 2 B
 recon + 1/16 B TU map per sample.
 
-cpu_baseline (rank 0, N=1 only): the CPU restatement in oracle/ ("port") on a
+cpu_baseline (--full; rank 0, N=1 only): the CPU restatement in oracle/ ("port") on a
 bounded sample of the same workload, on all of the job's host threads (config
 2) and on one thread; the sample's GPU outputs are checked bit-exact against it.
 """
@@ -101,7 +112,14 @@ def parse_args(argv=None):
                          "one chunk per rank)")
     ap.add_argument("--check", action="store_true", help="config 4, N>1: rank 0 compares the gathered recon with "
                                                           "an unsharded run")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: the streaming-copy "
+                         "rates of the roofline, the cpu_baseline legs with their bit-exact check, and (N > 1) the "
+                         "gather-inclusive phase; a plain run sets up, warms up, times --steps steps and prints")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed as DIR/<name>.npy (float32; a fixed "
+                         "seeded sample of an output too large to keep whole, at most 64 MB in all)")
     ap.add_argument("--launcher-selftest", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args(argv)
     if a.frames is None:
@@ -267,6 +285,28 @@ def reduce_max_sum(dist, dev, maxes, sums):
     return [float(x) for x in t], [float(x) for x in u]
 
 
+DUMP_BYTES = 64 * 10 ** 6      # --dump-outputs: upper bound for all the .npy files of one rank
+DUMP_SEED = 20240611           # the sample's own seed: the same elements whatever --seed is
+
+
+def dump_outputs(dirname, arrays, rank, world):
+    """--dump-outputs: the device tensors the timed path's caller receives, as
+    DIR/<name>.npy in float32 (every level / sample / map value is an integer
+    far below 2^24, so float32 holds it exactly).  An array that fits its share
+    of DUMP_BYTES is written whole; of a larger one the elements at sorted
+    indices drawn once from DUMP_SEED (a function of the array's length only).
+    Ranks above 0 write <name>_rank<r>.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    cap = (DUMP_BYTES - 4096 * len(arrays)) // (4 * len(arrays))   # float32 elements per array (.npy headers aside)
+    for name, t in arrays.items():
+        flat = t.reshape(-1)
+        if flat.numel() > cap:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), size=cap, dtype=np.int64))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        suffix = "" if world == 1 or rank == 0 else f"_rank{rank}"
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), flat.to(torch.float32).cpu().numpy())
+
+
 class OverlappedGather:
     """The exchange step on a side stream: gather(k) waits for compute(k) and
     runs under compute(k+1); the two output buffers alternate, and compute(k+2)
@@ -402,9 +442,11 @@ def run_cfg2(args, dist, world, rank, dev):
     (elapsed, kern_ms), (blocks_all, rate_sum) = reduce_max_sum(dist, dev, (elapsed, kern_ms),
                                                                 (nblk, nblk / (kern_ms * 1e-3)))
     value = blocks_all * args.steps / elapsed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"levels": outs[0][:layout.total_elems]}, rank, world)
 
     gather = None
-    if dist and args.gather_steps > 0:
+    if args.full and dist and args.gather_steps > 0:
         outs.append(torch.zeros_like(outs[0]))
         gf = args.frames if args.gather_frames is None else args.gather_frames
         frac = min(1.0, gf / args.frames)
@@ -430,9 +472,11 @@ def run_cfg2(args, dist, world, rank, dev):
     if rank != 0:
         return None
     achieved = nblk * BYTES_PER_BLOCK / (kern_ms * 1e-3) / 1e9
-    tmp = torch.empty_like(res)   # (outs[0] keeps the levels the cpu_baseline leg compares)
-    copy_gbs, torch_copy_gbs = device_copy_GBps(res, tmp, stream)   # context, after the timed region
-    del tmp
+    copy_gbs = torch_copy_gbs = None
+    if args.full:
+        tmp = torch.empty_like(res)   # (outs[0] keeps the levels the cpu_baseline leg compares)
+        copy_gbs, torch_copy_gbs = device_copy_GBps(res, tmp, stream)   # context, after the timed region
+        del tmp
     cfg_key = f"fwd8x8_qp{args.qp}_4k_yuv420_f{args.frames}_v{args.variant}_n{world}"
     line = {
         "metric": METRIC, "value": value, "unit": "blocks/s", "n_gpus": world, "steps": args.steps,
@@ -459,7 +503,7 @@ def run_cfg2(args, dist, world, rank, dev):
     }
     if gather:
         line["gather_inclusive"] = gather
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(outs[0], res, fe, frames_global, args.qp, args.cpu_seconds)
     return line
 
@@ -624,10 +668,13 @@ def run_cfg4(args, dist, world, rank, dev):
                                               [my_samples, my_samples / (kern_ms * 1e-3)] + me.tu_counts())
     samples_all, rate_sum, tu_all = sums[0], sums[1], sums[2:]
     value = samples_all * args.steps / elapsed
+    if args.dump_outputs:   # levels widened to the reference's int32 (the spill plane is only defined where it is used)
+        maps = {f"tu_map_{n}_band{i}": m for i, w in enumerate(me.work) for n, m in (("luma", w[4]), ("chroma", w[5]))}
+        dump_outputs(args.dump_outputs, dict({"levels": me.widen(lvl), "recon": recs[0]}, **maps), rank, world)
 
     sizes = [shard.cfg4_packed_elems(r, world, nf, W, H) for r in range(world)]
     gather, check = None, None
-    if dist and args.gather_steps > 0:
+    if (args.full or args.check) and dist and args.gather_steps > 0:   # --check compares what the gather delivered
         recs.append(me.new_rec())
         packed = [torch.zeros(max(sizes), dtype=torch.uint8, device=dev) for _ in range(2)]
         og = OverlappedGather(dist, dev, sizes, torch.uint8)
@@ -682,7 +729,7 @@ def run_cfg4(args, dist, world, rank, dev):
         line["gather_inclusive"] = gather
     if check is not None:
         line["gathered_recon_equals_unsharded"] = check
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline_cfg4(me, src, me.widen(lvl), recs[0], args, fe)
     return line
 

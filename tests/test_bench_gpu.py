@@ -43,7 +43,7 @@ def _check_common(d, steps):
 
 
 def test_bench_headline_line():
-    d = _run(["--frames", "2", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0.5"])
+    d = _run(["--full", "--frames", "2", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0.5"])
     _check_common(d, 3)
     assert d["unit"] == "blocks/s" and d["config"]["blocks_per_launch"] == 2 * 194400
     assert d["cpu_baseline"]["gpu_levels_bit_exact_on_sample"] is True
@@ -61,8 +61,34 @@ def test_bench_headline_line():
     assert rn["kind"] == "reference" and rn["value"] > 0 and "not the GPU box" in rn["host"]
 
 
+def test_bench_plain_run_is_lean_and_dumps_its_levels(tmp_path):
+    """Without --full the line keeps the headline keys but runs none of the side
+    measurements; --dump-outputs writes the last step's levels (one 4K frame fits
+    whole), reproducible from the seed: the same generator call in this process
+    gives the input whose oracle levels the dump must equal."""
+    import numpy as np
+    import torch
+    from oracle import oracle as O
+    d = _run(["--frames", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert KEYS <= set(d) and d["steps"] == 2 and d["dtype"] == "int32" and d["unit"] == "blocks/s"
+    assert abs(d["value"] * d["ms_per_step"] / 1e3 - 194400) / 194400 < 1e-6
+    assert d["cpu_baseline"] is None and "gather_inclusive" not in d
+    rf = d["roofline"]
+    assert rf["stream_copy_GBps"] is None and rf["torch_copy_GBps"] is None and 0 < rf["frac"] < 1
+    assert [p.name for p in tmp_path.iterdir()] == ["levels.npy"]
+    lv = np.load(tmp_path / "levels.npy")
+    W, H = 3840, 2160
+    assert lv.dtype == np.float32 and lv.shape == (W * H * 3 // 2,)
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(1234)
+    res = torch.randint(-255, 256, (lv.size,), dtype=torch.int16, device="cuda", generator=gen).cpu().numpy()
+    assert np.array_equal(lv[:W * H].reshape(H, W), O.fwd8x8_quant_plane(res[:W * H].reshape(H, W), 32, True))
+    u = res[W * H:W * H * 5 // 4].reshape(H // 2, W // 2)
+    assert np.array_equal(lv[W * H:W * H * 5 // 4].reshape(u.shape), O.fwd8x8_quant_plane(u, 32, True))
+
+
 def test_bench_config4_line():
-    d = _run(["--config", "4", "--frames", "2", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.5"])
+    d = _run(["--full", "--config", "4", "--frames", "2", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.5"])
     _check_common(d, 2)
     assert d["unit"] == "samples/s" and d["cpu_baseline"]["gpu_outputs_bit_exact_on_sample"] is True
     assert d["cpu_baseline"]["cores"] > 1 and d["cpu_baseline"]["value_1thread"] > 0

@@ -112,6 +112,27 @@ def test_cfg4_band_local_planes_need_only_the_halo(world):
                         assert np.array_equal(got[0][rows], exp[0][rows]) and np.array_equal(got[1][rows], exp[1][rows])
 
 
+def test_dump_outputs_keeps_small_arrays_whole_and_samples_large_ones(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy files within the byte budget; an array above
+    its share is cut to the same sorted, seeded sample on every call."""
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1 << 20)
+    cap = ((1 << 20) - 2 * 4096) // 8
+    small = torch.arange(-500, 500, dtype=torch.int16)
+    big = (torch.arange(3 * cap, dtype=torch.int64) % 1021).to(torch.int32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "big": big}, 0, 1)
+    bench.dump_outputs(str(tmp_path / "a"), {"small": small}, 1, 2)
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["big.npy", "small.npy", "small_rank1.npy"]
+    s, b = np.load(tmp_path / "a" / "small.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert s.dtype == b.dtype == np.float32 and np.array_equal(s, small.numpy()) and b.shape == (cap,)
+    assert sum(p.stat().st_size for p in (tmp_path / "b").iterdir()) <= 1 << 20
+    assert np.array_equal(b, np.load(tmp_path / "b" / "big.npy"))
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, big.numel(), size=cap, dtype=np.int64))
+    assert np.array_equal(b, big.numpy()[idx])
+
+
 def test_bench_inputs_travel_to_the_gpu_box():
     """bench.py reads profiles/pmc_traffic.json for roofline.traffic: no
     .gpurunignore pattern may keep it (or the built library) off the GPU box."""

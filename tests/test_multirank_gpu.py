@@ -23,7 +23,7 @@ BENCH = os.path.join(ROOT, "bench.py")
 def _run(args, timeout=240):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(NH_DIST_BACKEND="gloo", NH_FORCE_DEVICE="0")
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--no-cpu-baseline"] + args, env=env,
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--full", "--no-cpu-baseline"] + args, env=env,
                        capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -33,6 +33,8 @@ TAG=${TAG:-r03}
 VALU_CFGS=${VALU_CFGS:-3,4b,5b,closed,closed4}
 STEPS=${STEPS:-20}
 FRAMES=${FRAMES:-128}
+# every bench.py step below wants the whole line (copy rates, cpu_baseline, the gather phase of the rehearsals)
+BENCH_ARGS="--full ${BENCH_ARGS:-}"
 PMC3="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_INSTS_BRANCH SQ_INSTS_MFMA SQ_INSTS_VMEM_RD"
 PMC4="SQ_INSTS_VMEM_WR SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_CVT SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_TRANS_F32"
 PT="python -u -m pytest -x -q --timeout 120 --timeout-method thread"

@@ -64,7 +64,13 @@ def citations():
 
 
 def tracked_profiles() -> list[str]:
-    out = subprocess.run(["git", "ls-files", "profiles"], cwd=ROOT, capture_output=True, text=True, check=True).stdout
+    """The profiles/ files git tracks; [] where git cannot answer (an exported tree without .git, a
+    checkout owned by another user, no git installed): the caller then walks profiles/ itself."""
+    try:
+        out = subprocess.run(["git", "ls-files", "profiles"], cwd=ROOT, capture_output=True, text=True,
+                             check=True).stdout
+    except (subprocess.CalledProcessError, OSError):
+        return []
     return [ln for ln in out.splitlines() if ln]
 
 
