@@ -336,6 +336,32 @@ int nh_intra_rdo_planes_closed(const int16_t* d_src, const nh_plane_set* sets, i
                                void* d_work, void* stream);
 int nh_intra_rdo_closed_status(const void* d_work, int* status, void* stream);
 
+/* ---- Closed-loop intra DECODER: modes + levels -> recon ----
+ * Stage R: res = inverse_transform(dequantize_block(level, qp)).astype(int16)
+ * (quant.py:82-123, transform.py:199-238, int32 wrap-around included) over every
+ * full 8x8 block of the plane sets; exact for EVERY level value of the input
+ * dtype.  lvl_bytes 2 (int16, as nh_fwd8x8_quant_planes writes) or 4 (int32, as
+ * nh_intra_rdo_planes* write); d_res int16, source layout; samples outside full
+ * blocks are left untouched.  Any pitch >= width and any base: 16-byte rows are
+ * used when base, pitch and strides are multiples of 8 elements (and both
+ * buffers 16-B aligned), scalar accesses otherwise -- same results. */
+int nh_dequant_inv8x8_planes(const void* d_lvl, int lvl_bytes, int16_t* d_res,
+                             const nh_plane_set* sets, int nsets, int qp, void* stream);
+/* The decoder of nh_intra_rdo_planes_closed: d_modes, d_lvl, the plane sets and
+ * qp are that call's (same mode-map layout, plane numbering, level / recon
+ * layouts), d_recon receives its reconstruction (0 outside full blocks).
+ * Stage R into d_recon, then the row wavefront: one prediction per block from
+ * the reconstruction built so far, + residual, clip.  d_work: caller-owned,
+ * nh_intra_decode_closed_workspace_bytes() bytes, 8-B aligned, zeroed by the
+ * call.  Status word as the encoder's, read with nh_intra_rdo_closed_status:
+ * 0 ok, 1 a wavefront wait could not complete, 2 a mode above 34 in d_modes
+ * (found by a pre-pass; the wavefront then returns at once and d_recon is
+ * unspecified). */
+int64_t nh_intra_decode_closed_workspace_bytes(const nh_plane_set* sets, int nsets);
+int nh_intra_decode_planes_closed(const uint8_t* d_modes, const int32_t* d_lvl,
+                                  const nh_plane_set* sets, int nsets, int qp,
+                                  int16_t* d_recon, void* d_work, void* stream);
+
 /* ---- Frame I/O and the frame-level intra driver ----
  * Frame.from_yuv420p / Plane.from_buffer + .astype(np.int16) (frame.py:44-54,
  * :87-110) and Frame.to_yuv420p / PackedFrame.to_yuv420p's .astype(np.uint8)

@@ -1177,6 +1177,149 @@ __global__ void k_zero_partial(int16_t* rec, ClosedSet S, int nplanes) {
 }
 
 // ===========================================================================
+// Closed-loop DECODER of config 3: mode map + levels
+// -> the encoder's reconstruction.  The residual of every block is already in
+// rec (stage R, k_dequant_inv8x8, earlier on the stream: no dependency between
+// blocks, so it stays off the wavefront); this kernel is the dependent part.
+// Schedule, tagged 64-bit line words, carried top-left sample, bounded poll and
+// status word are k_intra_rdo8_closed_tag's (same ClosedArgs / closed_ticket /
+// workspace layout).  Per block: poll the 8 words of the top and top-right
+// blocks, ONE prediction with one sample per lane (the mode is uniform, so
+// the three predictors are scalar branches), + residual (int16 wrap), clip,
+// publish the bottom row, store the 64 samples over the residual they came
+// from.  Neighbours live in registers: the top words in lanes 0..7, the left
+// column in lanes 8 r + 7 of the previous block's reconstruction; lanes fetch
+// them with ds_bpermute (no LDS allocation, no barrier).  Every neighbour is a
+// clipped 8-bit sample or 128, so the int16 prediction arithmetic of intra.py
+// never wraps.
+// ===========================================================================
+// Pre-pass: a mode above 34 (mode_to_angle refuses it) sets status 2; the
+// wavefront then returns at once instead of predicting from a bad angle.
+__global__ void __launch_bounds__(256) k_dec_check_modes(const uint8_t* __restrict__ modes, int64_t n,
+                                                         int32_t* status) {
+    bool bad = false;
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) bad |= modes[i] >= kModes;
+    if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicMax(status, 2);
+}
+
+template <int WAVES>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES))) k_intra_dec8_closed(ClosedArgs a) {
+    if (ld_sys(&a.work[1])) return;   // bad mode map: no row is claimed, nothing waits
+    const int lane = threadIdx.x, i = lane >> 3, j = lane & 7;
+    uint64_t* lines = reinterpret_cast<uint64_t*>(a.work + a.lines0);
+    for (;;) {
+        int t = 0;
+        if (lane == 0) t = atomicAdd(&a.work[0], 1);
+        const int row = __builtin_amdgcn_readfirstlane(t);
+        if (row >= a.total_rows) break;
+        int si, pl, by;
+        closed_ticket(a, row, si, pl, by);
+        if (NH_CLOSED_PRIO) {
+            if (si == a.prio_set) __builtin_amdgcn_s_setprio(2);
+            else __builtin_amdgcn_s_setprio(0);
+        }
+        const ClosedSet& S = a.set[si];
+        const int g = pl / S.ppg, c = pl - g * S.ppg;
+        const int y0 = by * 8, full_words = S.bw * 4;
+        // this lane's sample of block 0 of the row
+        int16_t* p = a.rec + S.base + (int64_t)g * S.group_stride + (int64_t)c * S.plane_stride +
+                     (int64_t)(y0 + i) * S.pitch + j;
+        const uint8_t* mrow = a.modes + S.mode0 + (int64_t)pl * S.bw * S.bh + (int64_t)by * S.bw;
+        uint64_t* line = lines + S.line0 + (int64_t)pl * S.lw;
+        const uint64_t tag = (uint64_t)(uint32_t)(by + 1) << 32;
+        int tl = 128;     // top[7] of the previous block: the next block's top-left (its line word is overwritten)
+        int prev = 128;   // previous block's reconstruction, this lane's sample (left column: lanes 8 r + 7)
+        int res_n = 0, m_n = 0;
+        if (S.bw > 0) {
+            res_n = p[0];
+            m_n = mrow[0];
+        }
+        bool stall = false;
+        for (int bx = 0; bx < S.bw; ++bx) {
+            const int x0 = bx * 8;
+            const int res = res_n, m = __builtin_amdgcn_readfirstlane(m_n);
+            if (bx + 1 < S.bw) {   // next block's residual and mode, under this block's wait
+                res_n = p[x0 + 8];
+                m_n = mrow[bx + 1];
+            }
+            uint32_t val = 0x00800080u;   // no row above: 128
+            if (by > 0) {
+                // lanes 0..7: words x0/2 .. x0/2+7 (samples x0 .. x0+15) of the row above; words past
+                // the last full block are never written and read as 0 without a wait
+                const int wi = x0 / 2 + lane;
+                const bool need = lane < 8 && wi < full_words;
+                val = 0;
+                int spins = 0;
+                for (;;) {
+                    bool ok = true;
+                    if (need) {
+                        const uint64_t v = ld_sys64(line + wi);
+                        ok = (int)(v >> 32) == by;
+                        val = (uint32_t)v;
+                    }
+                    if (__builtin_amdgcn_read_exec() == __ballot(ok)) break;
+                    __builtin_amdgcn_s_sleep(1);
+                    ++spins;
+                    if (spins > kSpinLimit || ((spins & 1023) == 0 && ld_sys(&a.work[1]))) {
+                        if (lane == 0) atomicMax(&a.work[1], 1);
+                        stall = true;
+                        break;
+                    }
+                }
+                if (__ballot(stall)) {
+                    stall = true;
+                    break;
+                }
+            }
+            // top sample k (0..15): half k & 1 of lane k >> 1's word; left sample k (0..7): lane 8 k + 7
+            auto top_s = [&](int k) { return (int)((uint32_t)__shfl((int)val, k >> 1, 64) >> ((k & 1) * 16)) & 0xffff; };
+            auto left_s = [&](int k) { return __shfl(prev, k * 8 + 7, 64); };
+            const int nt = by == 0 ? 16 : min(16, S.w - x0);        // top samples that exist (numpy slice truncation)
+            const int tlc = (by == 0 || bx == 0) ? 128 : tl;
+            const int top7 = (int)(__builtin_amdgcn_readlane((int)val, 3) >> 16) & 0xffff;
+            int pred;
+            if (m == 0) {          // planar, tr = top[7], bl = left[7] (intra.py:81-113)
+                const int tv = top_s(j), lv = left_s(i), bl = __builtin_amdgcn_readlane(prev, 63);
+                pred = ((7 - j) * lv + (j + 1) * top7 + (7 - i) * tv + (i + 1) * bl + 8) >> 4;
+            } else if (m == 1) {   // DC (intra.py:46-62)
+                const int tv = top_s(j), lv = left_s(i);
+                pred = (grp_sum<64>((i == 0 ? tv : 0) + (j == 0 ? lv : 0)) + 8) >> 4;
+            } else {               // angular (intra.py:116-207), reference array evaluated per sample
+                const int angle = intra_angle_alu(m);
+                const bool vert = m >= 18;
+                const int base = vert ? j : i, scan = vert ? i : j;
+                const int proj = (scan + 1) * angle, f = proj & 31, idx = base + 1 + (proj >> 5);
+                const int npri = vert ? nt : 8, nsec = vert ? 8 : nt;   // samples after the corner
+                const int inv = angle < 0 ? inv_angle_alu(angle) : 0, next = (8 * angle) >> 5;
+                auto ref = [&](int q) {   // ref[q], q in [-8, 17] (_build_ref_array)
+                    const int kp = max(0, min(q, npri) - 1);
+                    const int pj = q < 0 ? ((q + 1) * inv + 128) >> 8 : 0;
+                    const int ks = min(15, max(0, pj - 1));
+                    const int tv = top_s(vert ? kp : ks), lv = left_s(min(7, vert ? ks : kp));
+                    const int pv = vert ? tv : lv, sv = vert ? lv : tv;
+                    if (q > 0) return pv;
+                    if (q == 0) return tlc;
+                    if (!(angle < 0 && q >= next && pj < 1 + nsec)) return 0;
+                    return pj == 0 ? tlc : sv;
+                };
+                const int r0 = ref(idx), r1 = ref(idx + 1);
+                pred = f ? ((32 - f) * r0 + f * r1 + 16) >> 5 : r0;
+            }
+            // reconstruct_block (int16 wrap) + clip_to_pixel_range(., 8)
+            int v = (int)(int16_t)(uint16_t)(uint32_t)(pred + res);
+            v = min(255, max(0, v));
+            const int hi = __shfl(v, (lane + 1) & 63, 64);
+            // publish the bottom row first (the next row polls these words)
+            if (i == 7 && !(j & 1)) st_sys64(line + x0 / 2 + j / 2, tag | (uint32_t)v | ((uint32_t)hi << 16));
+            p[x0] = (int16_t)v;
+            prev = v;
+            tl = top7;
+        }
+        if (stall) break;
+    }
+}
+
+// ===========================================================================
 // Config 4: mixed 4/8/16/32 TU pipeline.
 //   tu_leaf      : the seeded quadtree's leaf containing a sample (<= 3 hashes);
 //   k_tu_process : one launch per TU size over the N-aligned positions of the
@@ -3379,13 +3522,14 @@ extern "C" int nh_tu_pipeline_plane(const int16_t* d_src, int w, int h, int pitc
                                  stream);
 }
 
-static int closed_layout(const nh_plane_set* sets, int nsets, ClosedArgs& a, int64_t& modes_total) {
+// min_w: the encoder needs one full block column; the decoder accepts any positive width
+static int closed_layout(const nh_plane_set* sets, int nsets, ClosedArgs& a, int64_t& modes_total, int min_w = 8) {
     if (!sets || nsets < 1 || nsets > NH_MAX_PLANE_SETS) return NH_EARG;
     int64_t rows = 0, planes = 0, modes = 0, lines = 0;
     a.max_bh = 0;
     for (int k = 0; k < nsets; ++k) {
         const nh_plane_set& p = sets[k];
-        if (p.width < 8 || p.height < 0 || p.pitch < p.width || p.planes_per_group < 1 || p.num_groups < 0 ||
+        if (p.width < min_w || p.height < 0 || p.pitch < p.width || p.planes_per_group < 1 || p.num_groups < 0 ||
             p.width > 65535 || p.height > 65535)
             return NH_EARG;
         ClosedSet& S = a.set[k];
@@ -3497,6 +3641,83 @@ extern "C" int nh_intra_rdo_planes_closed(const int16_t* d_src, const nh_plane_s
                 k_intra_rdo8_closed_tag<1, kClosedWide><<<waves, 64, 0, s>>>(a);
             }
         }
+    }
+    NH_HIP(hipGetLastError());
+    return NH_OK;
+}
+
+// Decoder layout: the encoder's (same workspace, mode map and line buffers), for any positive plane
+// size -- a plane narrower or lower than 8 has no full block and decodes to zeros.
+static int decode_layout(const nh_plane_set* sets, int nsets, ClosedArgs& a, int64_t& modes_total, const char* who) {
+    if (!sets) {
+        set_error(std::string(who) + ": null argument");
+        return NH_EARG;
+    }
+    if (nsets < 1 || nsets > NH_MAX_PLANE_SETS) {
+        set_error(std::string(who) + ": nsets must be 1.." + std::to_string(NH_MAX_PLANE_SETS));
+        return NH_EARG;
+    }
+    for (int k = 0; k < nsets; ++k) {
+        const nh_plane_set& p = sets[k];
+        if (p.width < 1 || p.height < 1 || p.pitch < p.width || p.planes_per_group < 1 || p.num_groups < 0 ||
+            (int64_t)p.planes_per_group * p.num_groups > 65535) {
+            set_error(std::string(who) + ": plane set must have positive sizes, pitch >= width, <= 65535 planes");
+            return NH_EARG;
+        }
+    }
+    if (closed_layout(sets, nsets, a, modes_total, 1)) {
+        set_error(std::string(who) + ": bad plane sets (sizes <= 65535, < 2^30 block rows)");
+        return NH_EARG;
+    }
+    return NH_OK;
+}
+
+extern "C" int64_t nh_intra_decode_closed_workspace_bytes(const nh_plane_set* sets, int nsets) {
+    ClosedArgs a;
+    int64_t m = 0;
+    if (decode_layout(sets, nsets, a, m, "nh_intra_decode_closed_workspace_bytes")) return -1;
+    return 4ll * a.lines0 + 8ll * a.lines_total;
+}
+
+extern "C" int nh_intra_decode_planes_closed(const uint8_t* d_modes, const int32_t* d_lvl, const nh_plane_set* sets,
+                                             int nsets, int qp, int16_t* d_recon, void* d_work, void* stream) {
+    if (!d_modes || !d_lvl || !d_recon || !d_work) {
+        set_error("nh_intra_decode_planes_closed: null argument");
+        return NH_EARG;
+    }
+    ClosedArgs a{};
+    int64_t modes_total = 0;
+    NH_TRY(decode_layout(sets, nsets, a, modes_total, "nh_intra_decode_planes_closed"));
+    if ((uintptr_t)d_work & 7) {
+        set_error("nh_intra_decode_planes_closed: workspace must be 8-byte aligned");
+        return NH_EARG;
+    }
+    a.rec = d_recon;
+    a.modes = const_cast<uint8_t*>(d_modes);   // read only (the encoder's argument block)
+    a.work = (int32_t*)d_work;
+    a.order = 1;
+    a.prio_set = 0;
+    for (int k = 1; k < a.nsets; ++k)
+        if (a.set[k].bw + 2 * a.set[k].bh > a.set[a.prio_set].bw + 2 * a.set[a.prio_set].bh) a.prio_set = k;
+    hipStream_t s = as_stream(stream);
+    NH_HIP(hipMemsetAsync(d_work, 0, 4ull * a.lines0 + 8ull * a.lines_total, s));
+    for (int k = 0; k < nsets; ++k) {
+        const int np = sets[k].planes_per_group * sets[k].num_groups;
+        if (np > 0) k_zero_partial<<<dim3(64, np), 256, 0, s>>>(d_recon, a.set[k], np);
+    }
+    // stage R: every block's residual into d_recon (the wavefront reads neighbours only from the
+    // line words, so a block's residual is read from, and its recon written to, the same place)
+    NH_TRY(nh_dequant_inv8x8_planes(d_lvl, 4, d_recon, sets, nsets, qp, stream));
+    if (modes_total > 0)
+        k_dec_check_modes<<<(unsigned)std::min<int64_t>(1024, (modes_total + 255) / 256), 256, 0, s>>>(
+            d_modes, modes_total, (int32_t*)d_work + 1);
+    if (a.total_rows > 0) {
+        // persistent waves: one per row, capped at what can be resident
+        int cus = 0, per_cu = 0;
+        NH_TRY(device_cus(&cus));
+        NH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_intra_dec8_closed<1>, 64, 0));
+        const int64_t cap = (int64_t)std::max(1, per_cu) * cus;
+        k_intra_dec8_closed<1><<<(unsigned)(a.total_rows < cap ? a.total_rows : cap), 64, 0, s>>>(a);
     }
     NH_HIP(hipGetLastError());
     return NH_OK;

@@ -9,6 +9,8 @@ launch the gfx950 kernels through the C ABI on the tensor's current stream.
   fwd_transform_batch / inv_transform_batch / quant_batch / dequant_batch
   intra_rdo_plane     -- config 3: 35-mode RDO per 8x8 block of a plane; intra_rdo_planes: over plane sets
   intra_rdo_closed    -- config 3 in closed loop (row wavefront); _yuv420_stream: in batches, several in flight
+  dequant_inv8x8      -- decoder stage R: dequantise + inverse 8x8 DCT over plane sets (fwd8x8_quant's mirror)
+  intra_decode_closed -- the decoder of intra_rdo_closed: modes + levels -> its reconstruction
   tu_pipeline_plane   -- config 4: mixed 4..32 TU reconstruction chain on a plane
   tu_pipeline_planes_compact / tu_levels_widen -- config 4 with exact int16 levels (+ int32 spill)
   tc32_plane          -- config 5: 32x32 chain, butterfly or matrix-core variants
@@ -335,6 +337,69 @@ def intra_rdo_closed(src, sets: Sequence[PlaneSet], qp: int = 32, lvl=None, rec=
     if status.value:
         raise RuntimeError("intra_rdo_closed: the wavefront stalled (device status word set)")
     return modes[:nmodes], lvl, rec, sse[:nplanes]
+
+
+def dequant_inv8x8(lvl, sets: Sequence[PlaneSet], qp: int = 32, out=None, stream=None):
+    """Stage R of the decoder, the mirror of ``fwd8x8_quant``:
+    inverse_transform(dequantize_block(level, qp)).astype(int16) on every full
+    8x8 block of the int16 or int32 level planes described by ``sets`` inside
+    ``lvl``; exact for every level value of the dtype.  The residual lands at the
+    same raster positions of ``out`` (int16, same shape); samples outside full
+    blocks are left as they are.  Any pitch >= width and any base."""
+    torch = _torch()
+    if not isinstance(lvl, torch.Tensor) or lvl.dtype not in (torch.int16, torch.int32):
+        raise TypeError("dequant_inv8x8(lvl): expected an int16 or int32 CUDA/HIP torch tensor")
+    _need(lvl, lvl.dtype, "dequant_inv8x8(lvl)")
+    if out is None:
+        out = torch.zeros(lvl.shape, dtype=torch.int16, device=lvl.device)
+    _need(out, torch.int16, "dequant_inv8x8(out)")
+    sets_fit(sets, min(lvl.numel(), out.numel()), "dequant_inv8x8")
+    arr = (PlaneSet * len(sets))(*sets)
+    check(_lib.load().nh_dequant_inv8x8_planes(lvl.data_ptr(), lvl.element_size(), out.data_ptr(), arr, len(sets),
+                                               int(qp), C.c_void_p(_stream(stream, lvl.device))), "dequant_inv8x8")
+    return out
+
+
+def intra_decode_closed(modes, lvl, sets: Sequence[PlaneSet], qp: int = 32, rec=None, stream=None):
+    """The decoder of ``intra_rdo_closed``: from that call's
+    ``modes`` (uint8, its layout), ``lvl`` (int32, source layout), ``sets`` and
+    ``qp``, rebuild its reconstruction -- stage R, then one prediction per block
+    in closed loop on the row wavefront.  Returns recon int16 (source layout, 0
+    outside full blocks).  A mode above 34 raises ValueError."""
+    torch = _torch()
+    _need(lvl, torch.int32, "intra_decode_closed(lvl)")
+    _need(modes, torch.uint8, "intra_decode_closed(modes)")
+    if modes.device != lvl.device:
+        raise ValueError("intra_decode_closed: modes and lvl on different devices")
+    sets_fit(sets, lvl.numel(), "intra_decode_closed")
+    L = _lib.load()
+    arr = (PlaneSet * len(sets))(*sets)
+    wb = int(L.nh_intra_decode_closed_workspace_bytes(arr, len(sets)))
+    if wb < 0:
+        raise ValueError("intra_decode_closed: bad plane sets")
+    nmodes = sum((s.width // 8) * (s.height // 8) * s.planes_per_group * s.num_groups for s in sets)
+    if modes.numel() < nmodes:
+        raise ValueError(f"intra_decode_closed: {modes.numel()} modes for {nmodes} blocks")
+    if rec is None:
+        rec = torch.zeros(lvl.shape, dtype=torch.int16, device=lvl.device)
+    _need(rec, torch.int16, "intra_decode_closed(rec)")
+    if rec.device != lvl.device:
+        raise ValueError("intra_decode_closed: rec and lvl on different devices")
+    if rec.numel() < lvl.numel():
+        raise ValueError("intra_decode_closed: rec smaller than lvl")
+    if nmodes == 0:   # no full block anywhere: the device still zeroes rec, but reads no mode
+        modes = torch.zeros(1, dtype=torch.uint8, device=lvl.device)
+    work = torch.empty((wb + 3) // 4, dtype=torch.int32, device=lvl.device)
+    st = C.c_void_p(_stream(stream, lvl.device))
+    check(L.nh_intra_decode_planes_closed(modes.data_ptr(), lvl.data_ptr(), arr, len(sets), int(qp), rec.data_ptr(),
+                                          work.data_ptr(), st), "intra_decode_closed")
+    status = C.c_int(0)
+    check(L.nh_intra_rdo_closed_status(work.data_ptr(), C.byref(status), st))
+    if status.value == 2:
+        raise ValueError("intra_decode_closed: a mode above 34 in the mode map")
+    if status.value:
+        raise RuntimeError("intra_decode_closed: the wavefront stalled (device status word set)")
+    return rec
 
 
 def intra_rdo_closed_yuv420_stream(src, width: int, height: int, num_frames: int, qp: int = 32,

@@ -21,6 +21,10 @@
   closed  config 3 in CLOSED loop (neighbours from the reconstruction, wavefront
         schedule) over a batch of 1080p YUV420 frames; with --check, frame 0's
         luma against the oracle.
+  decode  (not in the default list) the decoder: dequant_inv8x8 on the 4K YUV420 stream of
+        config 2 (int16 levels) alternating with fwd8x8_quant on the same plane sets, and
+        intra_decode_closed on --closed-frames 1080p YUV420 frames alternating with the
+        intra_rdo_closed call whose outputs it decodes; both times and their ratio per line.
 
 Synthetic 8-bit content (gradient + seeded noise) resident in HBM; HIP events
 on the launch stream; one JSON line per config.
@@ -61,6 +65,25 @@ def timed(fn, reps):
     torch.cuda.synchronize()
     ts = sorted(a.elapsed_time(b) for a, b in evs)
     return ts[len(ts) // 2]
+
+
+def timed_pair(fa, fb, reps):
+    """Medians of fa and fb timed alternately (a, b, a, b, ...) in this process."""
+    st = torch.cuda.current_stream()
+    fa()
+    fb()
+    torch.cuda.synchronize()
+    evs = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(reps)]
+    for e in evs:
+        e[0].record(st)
+        fa()
+        e[1].record(st)
+        fb()
+        e[2].record(st)
+    torch.cuda.synchronize()
+    ta = sorted(e[0].elapsed_time(e[1]) for e in evs)
+    tb = sorted(e[1].elapsed_time(e[2]) for e in evs)
+    return ta[len(ta) // 2], tb[len(tb) // 2]
 
 
 def psnr_dev(a, b, peak=255):
@@ -131,6 +154,7 @@ def main():
     ap.add_argument("--configs", default="3,4,4b,5,closed,closed4,enc,io")
     ap.add_argument("--enc-frames", type=int, default=64)
     ap.add_argument("--closed-frames", type=int, default=64)
+    ap.add_argument("--decode-frames", type=int, default=128, help="decode: 4K YUV420 frames of the stage-R line")
     ap.add_argument("--ab", action="store_true", help="run on the A/B library (libnanohevc_ab.so: NH_* knobs read)")
     ap.add_argument("--lib", default=None, help="A/B: run on another build of libnanohevc.so (e.g. tools/_ab/...)")
     args = ap.parse_args()
@@ -552,6 +576,51 @@ def main():
                               "repeats_equal_single_call": bool((rec2.view(nb_, -1) == rec.view(1, -1)).all()) and
                               int(sse2[0].item()) == int(sse[0].item())}), flush=True)
             del big, lvl2, rec2
+
+    if "decode" in cfgs:
+        # line 1: stage R against the forward kernel, same plane sets, same bytes (int16 in, int16 out)
+        W4, H4, nf4 = 3840, 2160, args.decode_frames
+        fe4 = gpu.yuv420_frame_elems(W4, H4)
+        sets4 = gpu.yuv420_plane_sets(nf4, W4, H4)
+        g = torch.Generator(device="cuda")
+        g.manual_seed(21)
+        res4 = torch.randint(-255, 256, (nf4 * fe4,), device="cuda", generator=g, dtype=torch.int16)
+        lvl4 = torch.zeros_like(res4)
+        out4 = torch.zeros_like(res4)
+        gpu.fwd8x8_quant(res4, sets4, args.qp, out=lvl4)
+        ms_f, ms_r = timed_pair(lambda: gpu.fwd8x8_quant(res4, sets4, args.qp, out=out4),
+                                lambda: gpu.dequant_inv8x8(lvl4, sets4, args.qp, out=out4), max(4, args.reps))
+        nblk4 = gpu.blocks_in(sets4)
+        print(json.dumps({"config": "decode stage R: dequant_inv8x8 (int16 levels) vs fwd8x8_quant, alternating, "
+                                    "4K YUV420 stream of config 2", "frames": nf4, "qp": args.qp,
+                          "fwd8x8_quant_ms": ms_f, "dequant_inv8x8_ms": ms_r, "ratio_inv_over_fwd": ms_r / ms_f,
+                          "fwd_blocks_per_s": nblk4 / ms_f * 1e3, "inv_blocks_per_s": nblk4 / ms_r * 1e3,
+                          "inv_GBps": nblk4 * 256 / ms_r / 1e6, "knobs": knobs}), flush=True)
+        del res4, lvl4, out4
+        # line 2: the decoder against the closed-loop encoder whose outputs it decodes
+        W, H = 1920, 1080
+        nf = args.closed_frames
+        planes = []
+        for f in range(nf):
+            planes += [synth_plane(H, W, 11 + 3 * f).reshape(-1), synth_plane(H // 2, W // 2, 12 + 3 * f).reshape(-1),
+                       synth_plane(H // 2, W // 2, 13 + 3 * f).reshape(-1)]
+        stream = torch.cat(planes)
+        sets = gpu.yuv420_plane_sets(nf, W, H)
+        lvl = torch.zeros(stream.shape, dtype=torch.int32, device="cuda")
+        rec = torch.zeros(stream.shape, dtype=torch.int16, device="cuda")
+        dec = torch.zeros(stream.shape, dtype=torch.int16, device="cuda")
+        modes, _, _, _ = gpu.intra_rdo_closed(stream, sets, args.qp, lvl=lvl, rec=rec)
+        ms_e, ms_d = timed_pair(lambda: gpu.intra_rdo_closed(stream, sets, args.qp, lvl=lvl, rec=rec),
+                                lambda: gpu.intra_decode_closed(modes, lvl, sets, args.qp, rec=dec),
+                                max(3, args.reps // 2))
+        res_t = torch.zeros(stream.shape, dtype=torch.int16, device="cuda")
+        ms_stage_r = timed(lambda: gpu.dequant_inv8x8(lvl, sets, args.qp, out=res_t), max(3, args.reps // 2))
+        print(json.dumps({"config": "decode: intra_decode_closed vs the intra_rdo_closed call it decodes, alternating, "
+                                    "1080p YUV420 frames", "frames": nf, "qp": args.qp,
+                          "encode_ms_per_frame": ms_e / nf, "decode_ms_per_frame": ms_d / nf,
+                          "ratio_decode_over_encode": ms_d / ms_e,
+                          "stage_r_int32_ms_per_frame": ms_stage_r / nf,
+                          "decode_equals_encoder_recon": bool(torch.equal(dec, rec)), "knobs": knobs}), flush=True)
 
 
 if __name__ == "__main__":
