@@ -16,6 +16,7 @@
 #include "nh_internal.hpp"
 #include "nh_tree.hpp"
 #include "nh_packed.hpp"
+#include "nh_closed_ticket.hpp"
 #include "nh_f16mma.hpp"
 #include "nh_ldsdma.hpp"
 #define NH_MOSAIC_TABLE c_mosaic_cl
@@ -988,45 +989,8 @@ __device__ __forceinline__ void st_sys64(uint64_t* p, uint64_t v) {
 // The winner hands its recon / levels to the wave through LDS and the 64
 // lanes store one sample each (2 store instructions instead of 128
 // single-lane ones on the row's critical path).
-// Ticket -> (set, plane, block row).  order 0: plane-major (every row of
-// plane 0, then plane 1, ...).  order 1: row-major across planes (block row 0
-// of every plane of every set, then block row 1, ...): a row waits for the
-// row above from step 2*by of its plane on, so claiming rows in by order keeps
-// the 1,024 resident waves on rows that can start (plane-major parks the
-// lower rows of the first planes on their wavefront lag while later planes
-// wait for a slot): 874 -> 590 block steps for 8 1080p YUV420 frames in a
-// slot simulation.  Both orders claim row by-1 of a plane before row by, so a
-// wave only waits on a running or finished row.
-__device__ __forceinline__ void closed_ticket(const ClosedArgs& a, int t, int& si, int& pl, int& by) {
-    if (a.order == 0) {
-        si = 0;
-        for (int k = 1; k < a.nsets; ++k)
-            if (t >= a.set[k].row0) si = k;
-        const ClosedSet& S = a.set[si];
-        const int local = t - S.row0;
-        pl = local / S.bh;
-        by = local - pl * S.bh;
-        return;
-    }
-    // prefix(b) = rows with block row < b = sum_k np_k * min(b, bh_k); largest b with prefix(b) <= t
-    int lo = 0, hi = a.max_bh - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        int64_t pre = 0;
-        for (int k = 0; k < a.nsets; ++k) pre += (int64_t)a.set[k].np * min(mid, a.set[k].bh);
-        if (pre <= t) lo = mid; else hi = mid - 1;
-    }
-    by = lo;
-    int64_t r = t;
-    for (int k = 0; k < a.nsets; ++k) r -= (int64_t)a.set[k].np * min(by, a.set[k].bh);
-    si = 0;
-    for (int k = 0; k < a.nsets; ++k) {
-        if (by >= a.set[k].bh || a.set[k].np == 0) continue;
-        if (r < a.set[k].np) { si = k; break; }
-        r -= a.set[k].np;
-    }
-    pl = (int)r;
-}
+// Ticket -> (set, plane, block row): closed_ticket (nh_closed_ticket.hpp, shared
+// with the host property test of the map).
 
 template <int WAVES, int FORM = kClosedBoth>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES))) k_intra_rdo8_closed_tag(ClosedArgs a) {

@@ -58,11 +58,12 @@ CONFIGS = {
 # committed instruction counts still describe the build they run
 _HDRS = ["nh_common.hpp", "nh_internal.hpp", "nh_packed.hpp", "nh_tree.hpp", "nh_mfma.hpp", "nh_f16mma.hpp", "nh_mosaic.hpp",
          "nh_ldsdma.hpp"]
+_INTRALOOP = ["nh_intraloop.hip", "nh_closed_ticket.hpp"]
 SOURCES = {
-    "3": ["nh_intraloop.hip"] + _HDRS,
-    "closed": ["nh_intraloop.hip"] + _HDRS,
+    "3": _INTRALOOP + _HDRS,
+    "closed": _INTRALOOP + _HDRS,
     "4b": ["nh_ctu.hip"] + _HDRS,
-    "closed4": ["nh_intraloop.hip"] + _HDRS,
+    "closed4": _INTRALOOP + _HDRS,
     "5b": ["nh_ctu.hip", "nh_tc32.hip"] + _HDRS,
     "4bc": ["nh_ctu.hip"] + _HDRS,
     "5bc": ["nh_ctu.hip", "nh_tc32.hip"] + _HDRS,
