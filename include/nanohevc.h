@@ -362,6 +362,45 @@ int nh_intra_decode_planes_closed(const uint8_t* d_modes, const int32_t* d_lvl,
                                   const nh_plane_set* sets, int nsets, int qp,
                                   int16_t* d_recon, void* d_work, void* stream);
 
+/* ---- Config-4 closed-loop DECODER: TU map + pred-mode map +
+ * levels -> the reconstruction of nh_tu_pipeline_planes_closed ----
+ * One plane set per call; ctb 32 or 16; width and height multiples of 4.  d_tu and
+ * d_pm hold (h/4)*(w/4) bytes per plane, planes numbered g * planes_per_group + c:
+ * d_tu the log2 TU size per 4x4 unit as the encoder writes it, d_pm 1 = DC,
+ * 0 = planar (the reference's mode numbers), read at a TU's top-left unit.
+ * Every entry point returns NH_EARG, on the host and before any HIP call, for a
+ * ctb other than 16 / 32, a width or height that is no multiple of 4, an
+ * lvl_bytes other than 2 / 4 and a null pointer (nh_last_error has the text).
+ *
+ * nh_tu_closed_pred_map: the encoder-side post-pass.  From the encoder's source,
+ * reconstruction and TU map it recomputes every TU's DC and planar predictions
+ * (neighbours from d_recon, 128 at the plane border) and writes 1 where the DC
+ * residual energy is <= the planar one (int16-wrapping residual, int64 sums) to
+ * every unit of the TU.  TUs are independent: one parallel launch, no wavefront. */
+int nh_tu_closed_pred_map(const int16_t* d_src, const int16_t* d_recon, const uint8_t* d_tu,
+                          const nh_plane_set* set, int ctb, uint8_t* d_pm, void* stream);
+/* Stage R over a TU map: per TU (N = 4, 8, 16, 32)
+ *   res = inverse_transform(dequantize_block(level, qp), use_dst = is_luma && N == 4).astype(int16)
+ * in ring arithmetic mod 2^32: exact for EVERY level value of the input dtype
+ * (lvl_bytes 2 = int16, 4 = int32).  d_res int16, source layout.  The map is not
+ * validated here: values are clamped to 2..5, a bad map is memory-safe and its
+ * residual unspecified.  Any pitch >= width and any base (vector row pieces when
+ * base, pitch and strides are multiples of 4 samples, scalar accesses otherwise). */
+int nh_dequant_inv_tu_planes(const void* d_lvl, int lvl_bytes, int16_t* d_res, const uint8_t* d_tu,
+                             const nh_plane_set* set, int ctb, int is_luma, int qp, void* stream);
+/* The decoder: stage R into d_recon, a validity pre-pass over both maps, then the
+ * CTU-row wavefront (one prediction per TU from the reconstruction built so far,
+ * + residual with the int16 wrap, clip).  d_lvl int32, source layout.  d_work:
+ * caller-owned, nh_tu_decode_closed_workspace_bytes() bytes, 8-B aligned, zeroed
+ * by the call.  Status word read with nh_intra_rdo_closed_status: 0 ok, 1 a
+ * wavefront wait could not complete, 2 a bad map (d_tu is no partition of the
+ * plane into aligned squares of 4 .. ctb samples, or a d_pm value above 1): the
+ * wavefront then returns at once and d_recon is unspecified. */
+int64_t nh_tu_decode_closed_workspace_bytes(const nh_plane_set* set, int ctb);
+int nh_tu_decode_planes_closed(const uint8_t* d_tu, const uint8_t* d_pm, const int32_t* d_lvl,
+                               const nh_plane_set* set, int ctb, int is_luma, int qp,
+                               int16_t* d_recon, void* d_work, void* stream);
+
 /* ---- Frame I/O and the frame-level intra driver ----
  * Frame.from_yuv420p / Plane.from_buffer + .astype(np.int16) (frame.py:44-54,
  * :87-110) and Frame.to_yuv420p / PackedFrame.to_yuv420p's .astype(np.uint8)

@@ -94,6 +94,10 @@ SIGNATURES = {
     "nh_dequant_inv8x8_planes": ([P, I32, P, C.POINTER(PlaneSet), I32, I32, VP], I32),
     "nh_intra_decode_closed_workspace_bytes": ([C.POINTER(PlaneSet), I32], I64),
     "nh_intra_decode_planes_closed": ([P, P, C.POINTER(PlaneSet), I32, I32, P, P, VP], I32),
+    "nh_tu_closed_pred_map": ([P, P, P, C.POINTER(PlaneSet), I32, P, VP], I32),
+    "nh_dequant_inv_tu_planes": ([P, I32, P, P, C.POINTER(PlaneSet), I32, I32, I32, VP], I32),
+    "nh_tu_decode_closed_workspace_bytes": ([C.POINTER(PlaneSet), I32], I64),
+    "nh_tu_decode_planes_closed": ([P, P, P, C.POINTER(PlaneSet), I32, I32, I32, P, P, VP], I32),
     "nh_widen_u8_i16": ([P, P, I64, VP], I32),
     "nh_narrow_i16_u8": ([P, P, I64, VP], I32),
     "nh_encode_intra_planes": ([P, I32, C.POINTER(PlaneSet), I32, P, P, P, P, P, VP], I32),

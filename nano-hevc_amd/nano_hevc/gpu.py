@@ -19,6 +19,10 @@ launch the gfx950 kernels through the C ABI on the tensor's current stream.
   tu_pipeline_closed  -- config 4 in closed loop (CTU-row wavefront, TUs in z-order)
   tu_pipeline_closed_yuv420 -- the same over a YUV420 stream, luma and chroma wavefronts concurrent
   tu_pipeline_closed_yuv420_stream -- the same in batches of frames, several batches in flight
+  tu_pred_map_closed  -- the DC / planar choice per TU of a tu_pipeline_closed call, derived from its outputs
+  dequant_inv_tu      -- decoder stage R over a TU map (4x4 DST / DCT, 8, 16, 32), exact for every level
+  tu_decode_closed    -- the decoder of tu_pipeline_closed: TU map + pred-mode map + levels -> its reconstruction
+  tu_decode_closed_yuv420 -- the same over a YUV420 stream, luma and chroma wavefronts concurrent
   widen_u8 / narrow_u8 -- frame I/O casts (YUV420p bytes <-> int16 planes)
   encode_intra_yuv420 -- encode_frame_intra (DC vs planar per block) over a frame stream
   block_server_stop / block_server_set_idle_us / block_server_stats -- the per-block
@@ -710,6 +714,192 @@ def tu_pipeline_closed_yuv420(src, luma: PlaneSet, chroma: PlaneSet, seed: int, 
         _tu_closed_status(work_c, int(main.cuda_stream), "tu_pipeline_closed_yuv420 (chroma)")
         raise
     return lvl, rec, tu_luma, tu_chroma
+
+
+def _tu_map_need(t, pset: PlaneSet, dev, what):
+    """A per-4x4-unit map of one plane set: uint8, contiguous, on ``dev``, at least
+    planes * (h/4) * (w/4) entries; with two or more dimensions its trailing shape
+    must be the plane's (h/4, w/4)."""
+    torch = _torch()
+    _need(t, torch.uint8, what)
+    if t.device != dev:
+        raise ValueError(f"{what}: on {t.device}, the other tensors on {dev}")
+    h4, w4 = pset.height // 4, pset.width // 4
+    n = pset.planes_per_group * pset.num_groups * h4 * w4
+    if t.numel() < n:
+        raise ValueError(f"{what}: {t.numel()} entries for {n} 4x4 units")
+    if t.dim() >= 2 and tuple(t.shape[-2:]) != (h4, w4):
+        raise ValueError(f"{what}: trailing shape {tuple(t.shape[-2:])}, expected {(h4, w4)}")
+
+
+def _tu_set_check(pset: PlaneSet, ctb: int, what: str):
+    if int(ctb) not in (16, 32):
+        raise ValueError(f"{what}: ctb must be 16 or 32")
+    if pset.width % 4 or pset.height % 4 or pset.width < 4 or pset.height < 4:
+        raise ValueError(f"{what}: width and height must be positive multiples of 4")
+
+
+def tu_pred_map_closed(src, rec, tu, pset: PlaneSet, ctb: int, pm=None, stream=None):
+    """The pred-mode map of a ``tu_pipeline_closed`` call, derived
+    after the fact from that call's ``src``, ``rec`` and ``tu``: per TU 1 where the
+    encoder chose DC, 0 where it chose planar, written to every 4x4 unit of the TU.
+    Every TU is independent (its neighbours are finished reconstruction samples):
+    one parallel launch.  Returns pm uint8 (planes, h/4, w/4)."""
+    torch = _torch()
+    _need(src, torch.int16, "tu_pred_map_closed(src)")
+    _need(rec, torch.int16, "tu_pred_map_closed(rec)")
+    if rec.device != src.device:
+        raise ValueError("tu_pred_map_closed: src and rec on different devices")
+    _tu_set_check(pset, ctb, "tu_pred_map_closed")
+    sets_fit([pset], min(src.numel(), rec.numel()), "tu_pred_map_closed")
+    _tu_map_need(tu, pset, src.device, "tu_pred_map_closed(tu)")
+    planes = pset.planes_per_group * pset.num_groups
+    if pm is None:
+        pm = torch.zeros((planes, pset.height // 4, pset.width // 4), dtype=torch.uint8, device=src.device)
+    _tu_map_need(pm, pset, src.device, "tu_pred_map_closed(pm)")
+    check(_lib.load().nh_tu_closed_pred_map(src.data_ptr(), rec.data_ptr(), tu.data_ptr(), C.byref(pset), int(ctb),
+                                            pm.data_ptr(), C.c_void_p(_stream(stream, src.device))),
+          "tu_pred_map_closed")
+    return pm
+
+
+def dequant_inv_tu(lvl, tu, pset: PlaneSet, ctb: int, is_luma: bool = True, qp: int = 32, out=None, stream=None):
+    """Stage R of the config-4 decoder: per TU of the map ``tu``
+    inverse_transform(dequantize_block(level, qp), use_dst = is_luma and N == 4).astype(int16)
+    on the int16 or int32 level planes of ``pset`` inside ``lvl``; exact for every
+    level value of the dtype.  The residual lands at the same positions of ``out``
+    (int16).  The map is not validated here (``tu_decode_closed`` does): a bad one
+    is memory-safe and gives an unspecified residual."""
+    torch = _torch()
+    if not isinstance(lvl, torch.Tensor) or lvl.dtype not in (torch.int16, torch.int32):
+        raise TypeError("dequant_inv_tu(lvl): expected an int16 or int32 CUDA/HIP torch tensor")
+    _need(lvl, lvl.dtype, "dequant_inv_tu(lvl)")
+    _tu_set_check(pset, ctb, "dequant_inv_tu")
+    if out is None:
+        out = torch.zeros(lvl.shape, dtype=torch.int16, device=lvl.device)
+    _need(out, torch.int16, "dequant_inv_tu(out)")
+    if out.device != lvl.device:
+        raise ValueError("dequant_inv_tu: out and lvl on different devices")
+    sets_fit([pset], min(lvl.numel(), out.numel()), "dequant_inv_tu")
+    _tu_map_need(tu, pset, lvl.device, "dequant_inv_tu(tu)")
+    check(_lib.load().nh_dequant_inv_tu_planes(lvl.data_ptr(), lvl.element_size(), out.data_ptr(), tu.data_ptr(),
+                                               C.byref(pset), int(ctb), int(bool(is_luma)), int(qp),
+                                               C.c_void_p(_stream(stream, lvl.device))), "dequant_inv_tu")
+    return out
+
+
+def _tu_decode_launch(tu, pm, lvl, pset: PlaneSet, ctb: int, is_luma: bool, qp: int, rec, strm):
+    """Stream-ordered launch of the config-4 decoder over one plane set on the torch
+    stream ``strm``; returns (rec, workspace) -- the workspace holds the status word."""
+    torch = _torch()
+    _need(lvl, torch.int32, "tu_decode_closed(lvl)")
+    _tu_set_check(pset, ctb, "tu_decode_closed")
+    sets_fit([pset], lvl.numel(), "tu_decode_closed")
+    _tu_map_need(tu, pset, lvl.device, "tu_decode_closed(tu)")
+    _tu_map_need(pm, pset, lvl.device, "tu_decode_closed(pm)")
+    L = _lib.load()
+    wb = int(L.nh_tu_decode_closed_workspace_bytes(C.byref(pset), int(ctb)))
+    if wb < 0:
+        raise ValueError("tu_decode_closed: bad plane set (w, h multiples of 4) or CTB size")
+    with torch.cuda.device(lvl.device), torch.cuda.stream(strm):
+        if rec is None:
+            rec = torch.zeros(lvl.shape, dtype=torch.int16, device=lvl.device)
+        _need(rec, torch.int16, "tu_decode_closed(rec)")
+        if rec.device != lvl.device:
+            raise ValueError("tu_decode_closed: rec and lvl on different devices")
+        if rec.numel() < lvl.numel():
+            raise ValueError("tu_decode_closed: rec smaller than lvl")
+        work = torch.empty((wb + 7) // 8, dtype=torch.int64, device=lvl.device)
+        check(L.nh_tu_decode_planes_closed(tu.data_ptr(), pm.data_ptr(), lvl.data_ptr(), C.byref(pset), int(ctb),
+                                           int(bool(is_luma)), int(qp), rec.data_ptr(), work.data_ptr(),
+                                           C.c_void_p(int(strm.cuda_stream))), "tu_decode_closed")
+    return rec, work
+
+
+def _tu_decode_status(work, st: int, what: str):
+    status = C.c_int(0)
+    check(_lib.load().nh_intra_rdo_closed_status(work.data_ptr(), C.byref(status), C.c_void_p(st)))
+    if status.value == 2:
+        raise ValueError(f"{what}: bad map (tu is no partition into aligned squares of 4..ctb samples inside "
+                         "the plane, or a pm value above 1; status 2)")
+    if status.value:
+        raise RuntimeError("%s: the device wavefront stalled (status %d)" % (what, status.value))
+
+
+def tu_decode_closed(tu, pm, lvl, pset: PlaneSet, ctb: int, qp: int = 32, is_luma: bool = True, rec=None,
+                     stream=None):
+    """The decoder of ``tu_pipeline_closed``: from that call's
+    ``tu`` and ``lvl`` (int32, source layout), the pred-mode map ``pm`` of
+    ``tu_pred_map_closed``, ``pset``, ``ctb``, ``qp`` and ``is_luma`` rebuild its
+    reconstruction: stage R, then one prediction per TU in closed loop on the
+    CTU-row wavefront.  Map-driven: any ``tu`` that partitions every plane into
+    aligned squares of 4..ctb samples decodes, whatever made it; any other map, or
+    a ``pm`` value above 1, raises ValueError (``rec`` is then unspecified).
+    Returns recon int16 (source layout)."""
+    torch = _torch()
+    if not isinstance(lvl, torch.Tensor) or not lvl.is_cuda:
+        raise TypeError("tu_decode_closed(lvl): expected a CUDA/HIP torch tensor")
+    strm = stream if stream is not None else torch.cuda.current_stream(lvl.device)
+    st = _stream(strm, lvl.device)
+    rec, work = _tu_decode_launch(tu, pm, lvl, pset, ctb, is_luma, qp, rec, strm)
+    _tu_decode_status(work, st, "tu_decode_closed")
+    return rec
+
+
+def tu_decode_closed_yuv420(tu_luma, pm_luma, tu_chroma, pm_chroma, lvl, luma: PlaneSet, chroma: PlaneSet,
+                            qp: int = 32, rec=None, stream=None):
+    """The decoder of ``tu_pipeline_closed_yuv420``: the luma set (CTB 32) and the
+    chroma set (CTB 16) -- the two calls of ``tu_decode_closed`` -- as two concurrent
+    device wavefronts, the chroma one on a side stream forked from and joined back
+    into ``stream``; in sequence when the sets share elements.  Returns rec."""
+    torch = _torch()
+    if not isinstance(lvl, torch.Tensor) or not lvl.is_cuda:
+        raise TypeError("tu_decode_closed_yuv420(lvl): expected a CUDA/HIP torch tensor")
+    dev = lvl.device
+    main = stream if stream is not None else torch.cuda.current_stream(dev)
+    if main.device != dev:
+        raise ValueError(f"tu_decode_closed_yuv420: stream on {main.device} but lvl on {dev}")
+    if not sets_disjoint(luma, chroma):
+        # the two wavefronts would write shared rec elements concurrently: decode them in sequence
+        rec = tu_decode_closed(tu_luma, pm_luma, lvl, luma, 32, qp, True, rec, main)
+        return tu_decode_closed(tu_chroma, pm_chroma, lvl, chroma, 16, qp, False, rec, main)
+    side = _SIDE_STREAMS.get(dev.index)
+    if side is None:
+        side = _SIDE_STREAMS[dev.index] = torch.cuda.Stream(device=dev)
+    if rec is None:
+        with torch.cuda.device(dev), torch.cuda.stream(main):
+            rec = torch.zeros(lvl.shape, dtype=torch.int16, device=dev)
+    fork = torch.cuda.Event()
+    fork.record(main)
+    side.wait_event(fork)
+    work_y = work_c = None
+    try:
+        # luma first: its wavefront is the longer one and takes its slots before chroma's
+        rec, work_y = _tu_decode_launch(tu_luma, pm_luma, lvl, luma, 32, True, qp, rec, main)
+        _, work_c = _tu_decode_launch(tu_chroma, pm_chroma, lvl, chroma, 16, False, qp, rec, side)
+    finally:   # whatever was queued on the side stream is joined back, also when a check raised
+        join = torch.cuda.Event()
+        join.record(side)
+        main.wait_event(join)
+        if work_c is not None:
+            work_c.record_stream(main)
+    # one host round trip for both status words: chroma's ORed into a copy of luma's on `main`
+    with torch.cuda.device(dev), torch.cuda.stream(main):
+        both = work_y[:1].clone()
+        both.view(torch.int32)[1:2].bitwise_or_(work_c[:1].view(torch.int32)[1:2])
+    try:
+        _tu_decode_status(both, int(main.cuda_stream), "tu_decode_closed_yuv420")
+    except (ValueError, RuntimeError):   # name the set; a bad map (status 2) goes before a stall (status 1)
+        errs = []
+        for work, name in ((work_y, "luma"), (work_c, "chroma")):
+            try:
+                _tu_decode_status(work, int(main.cuda_stream), "tu_decode_closed_yuv420 (%s)" % name)
+            except (ValueError, RuntimeError) as e:
+                errs.append(e)
+        for e in sorted(errs, key=lambda e: not isinstance(e, ValueError)):
+            raise e
+        raise
+    return rec
 
 
 _PIPE_STREAMS = {}

@@ -25,6 +25,10 @@
         config 2 (int16 levels) alternating with fwd8x8_quant on the same plane sets, and
         intra_decode_closed on --closed-frames 1080p YUV420 frames alternating with the
         intra_rdo_closed call whose outputs it decodes; both times and their ratio per line.
+  decode4 (not in the default list) the config-4 decoder: tu_decode_closed_yuv420 on
+        --closed4-frames 4K YUV420 frames alternating with the tu_pipeline_closed_yuv420 call
+        whose outputs it decodes (asserted equal), plus the pred-map kernel alone and stage R
+        over the TU map next to dequant_inv8x8 on the same int32 bytes.
 
 Synthetic 8-bit content (gradient + seeded noise) resident in HBM; HIP events
 on the launch stream; one JSON line per config.
@@ -621,6 +625,53 @@ def main():
                           "ratio_decode_over_encode": ms_d / ms_e,
                           "stage_r_int32_ms_per_frame": ms_stage_r / nf,
                           "decode_equals_encoder_recon": bool(torch.equal(dec, rec)), "knobs": knobs}), flush=True)
+
+    if "decode4" in cfgs:
+        # the config-4 decoder against the closed-loop encoder call whose outputs it decodes
+        W, H, nf = 3840, 2160, args.closed4_frames
+        planes = []
+        for f in range(nf):
+            planes += [synth_plane(H, W, 40 + 3 * f).reshape(-1), synth_plane(H // 2, W // 2, 41 + 3 * f).reshape(-1),
+                       synth_plane(H // 2, W // 2, 42 + 3 * f).reshape(-1)]
+        stream = torch.cat(planes)
+        del planes
+        sy, suv = gpu.yuv420_plane_sets(nf, W, H)
+        lv = torch.zeros(stream.shape, dtype=torch.int32, device="cuda")
+        rc = torch.zeros(stream.shape, dtype=torch.int16, device="cuda")
+        dec = torch.zeros(stream.shape, dtype=torch.int16, device="cuda")
+        tuy = torch.zeros((nf, H // 4, W // 4), dtype=torch.uint8, device="cuda")
+        tuc = torch.zeros((2 * nf, H // 8, W // 8), dtype=torch.uint8, device="cuda")
+        pmy, pmc = torch.zeros_like(tuy), torch.zeros_like(tuc)
+        enc = lambda: gpu.tu_pipeline_closed_yuv420(stream, sy, suv, 1234, args.qp, lvl=lv, rec=rc, tu_luma=tuy,
+                                                    tu_chroma=tuc)
+        enc()
+
+        def run_map():
+            gpu.tu_pred_map_closed(stream, rc, tuy, sy, 32, pm=pmy)
+            gpu.tu_pred_map_closed(stream, rc, tuc, suv, 16, pm=pmc)
+
+        def run_stage_r():
+            gpu.dequant_inv_tu(lv, tuy, sy, 32, True, args.qp, out=dec)
+            gpu.dequant_inv_tu(lv, tuc, suv, 16, False, args.qp, out=dec)
+        run_map()
+        reps = max(3, args.reps // 4)
+        ms_e, ms_d = timed_pair(enc, lambda: gpu.tu_decode_closed_yuv420(tuy, pmy, tuc, pmc, lv, sy, suv, args.qp,
+                                                                         rec=dec), reps)
+        same = bool(torch.equal(dec, rc))
+        assert same, "decode4: the decoder's reconstruction differs from the encoder's"
+        ms_map = timed(run_map, reps)
+        sets8 = [sy, suv]
+        ms_r, ms_r8 = timed_pair(run_stage_r, lambda: gpu.dequant_inv8x8(lv, sets8, args.qp, out=dec), reps)
+        print(json.dumps({"config": "decode4: tu_decode_closed_yuv420 vs the tu_pipeline_closed_yuv420 call it decodes, "
+                                    "alternating, 4K YUV420 frames", "frames": nf, "qp": args.qp,
+                          "encode_ms_per_frame": ms_e / nf, "decode_ms_per_frame": ms_d / nf,
+                          "ratio_decode_over_encode": ms_d / ms_e,
+                          "pred_map_ms_per_frame": ms_map / nf,
+                          "stage_r_tu_int32_ms_per_frame": ms_r / nf,
+                          "dequant_inv8x8_int32_ms_per_frame": ms_r8 / nf,
+                          "ratio_stage_r_tu_over_inv8x8": ms_r / ms_r8,
+                          "dc_fraction_luma": float(pmy.float().mean().item()),
+                          "decode_equals_encoder_recon": same, "knobs": knobs}), flush=True)
 
 
 if __name__ == "__main__":
