@@ -238,6 +238,25 @@ int nh_intra_rdo_planes(const int16_t* d_src, const nh_plane_set* sets, int nset
                         uint8_t* d_modes, int32_t* d_lvl, int16_t* d_recon, int64_t* d_sse,
                         void* stream);
 
+/* Config 3 at every HEVC block size: the same 35-mode
+ * open-loop decision per full NxN block, N = block_size in {4, 8, 16, 32};
+ * use_dst selects the 4x4 DST-VII and is allowed only with block_size 4.
+ * Angular references are [tl] + 2N top / left samples, truncated at the right
+ * / bottom plane edge and extended by the reference's replicate-last rule.
+ * d_modes: (h/N)*(w/N) u8 per plane, planes in set order; d_lvl (int32) and
+ * d_recon (int16) in the source layout, only samples of full blocks written;
+ * d_sse (optional): one int64 per plane, the chosen SSEs added to it.  One
+ * launch per plane set; block_size 8 forwards to nh_intra_rdo_planes.
+ * Returns NH_EARG on the host, before any HIP call (text in nh_last_error), for
+ * a block_size outside {4, 8, 16, 32}, use_dst with block_size != 4, a QP
+ * outside 0..51 (not clamped), nsets outside 1..NH_MAX_PLANE_SETS, a null
+ * pointer or a bad plane set.  Any pitch >= width and any base: 16-byte row
+ * stores when base, pitch and strides are multiples of 8 elements and both
+ * output buffers are 16-B aligned, element stores otherwise -- same results. */
+int nh_intra_rdo_planes_n(const int16_t* d_src, const nh_plane_set* sets, int nsets,
+                          int block_size, int use_dst, int qp, uint8_t* d_modes,
+                          int32_t* d_lvl, int16_t* d_recon, int64_t* d_sse, void* stream);
+
 /* Config 4: mixed 4/8/16/32 TU pipeline on one plane over CTU rows
  * [row0, row1): seeded quadtree per CTB (ctb 32 luma / 16
  * chroma), per TU the __main__.py:165-178 DC-vs-planar choice then the full

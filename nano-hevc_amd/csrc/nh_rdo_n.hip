@@ -1,0 +1,555 @@
+// nh_rdo_n.hip -- config 3 at the other HEVC sizes: the 35-mode open-loop RDO
+// per full NxN block for N = 4 (DST or DCT), 16 and 32.
+//
+// Per block: neighbours from the source plane with the BlockView rules
+// (block.py:38-55; 128 outside the plane, numpy slice truncation of the 2N
+// angular references at the right / bottom edge), planar / DC / 33 angular
+// predictions (intra.py:46-62, :81-113, :116-207 with D5, D6, D8), and per mode
+// the chain of k_tu_process (nh_intraloop.hip): residual -> forward transform ->
+// quantize -> dequantize -> inverse transform -> reconstruct -> clip, cost =
+// SSE(orig, recon) in 64 bits.  Lowest (sse << 6 | mode) wins.
+//
+// Work maps:
+//   N = 4      a lane per (block, mode), the 4x4 in registers, 7 blocks x 35
+//              modes per 256-thread workgroup (as k_intra_rdo8 does for 8x8);
+//   N = 16, 32 N lanes per (block, mode) chain -- lane t does column t, then
+//              row t, through an LDS tile of pitch N + 1 (as k_tu_process) --
+//              7 chains per block, 5 rounds for the 35 modes, then chain 0 runs
+//              the winning mode once more and stores its levels and recon.  A
+//              workgroup is 224 lanes: one 32x32 block or two 16x16 blocks.
+//              The block's samples and its 4N + 1 reference samples are staged
+//              in LDS once for all 35 chains.  A chain lies inside one wave, so
+//              the only workgroup barriers are the two after staging and the
+//              one before the winner's round; between a chain's passes a
+//              wave-level barrier orders the LDS accesses (a wave's LDS
+//              instructions execute in program order).
+// Blocks are independent (open loop): no cross-workgroup wait of any kind.
+//
+// Multiplies: the chain is k_tu_process's, whose 24-bit multiplies are exact for
+// every int16 residual at every QP and size; tools/rdo_n_bounds.py enumerates the
+// operand bounds for the transforms used here (tests/test_rdo_n_host.py).
+#include <hip/hip_runtime.h>
+#include <climits>
+#include "nh_common.hpp"
+#include "nh_internal.hpp"
+
+namespace nh {
+namespace {
+
+constexpr int kModesN = 35;
+constexpr int kLaneSlots = 7;    // N = 4: blocks per workgroup
+constexpr int kChains = 7;       // N = 16 / 32: chains per block
+
+struct RdoNArgs {
+    const int16_t* src;
+    int32_t* lvl;
+    int16_t* recon;
+    uint8_t* modes;
+    unsigned long long* sse;     // one word per plane, or null
+    int32_t w, h, pitch;
+    QuantParams qp;
+    int32_t dq_scale, dq_per;
+    int32_t vec_out;             // every row start of lvl / recon is 16-B aligned
+    int64_t group_stride, plane_stride;
+    int32_t ppg;
+};
+
+__device__ __forceinline__ int32_t w16(int32_t v) { return (int32_t)(int16_t)(uint16_t)(uint32_t)v; }
+
+// INTRA_PRED_ANGLE[mode - 2] / INV_ANGLE[angle] for a per-lane mode without a
+// memory table (the forms of nh_intraloop.hip's intra_angle_alu / inv_angle_alu)
+__device__ __forceinline__ int angle_of(int mode) {
+    constexpr uint64_t kMag = 0ull | (2ull << 6) | (5ull << 12) | (9ull << 18) | (13ull << 24) | (17ull << 30) |
+                              (21ull << 36) | (26ull << 42) | (32ull << 48);
+    const int d = mode < 18 ? 10 - mode : mode - 26;
+    const int k = d < 0 ? -d : d;
+    const int m = (int)((kMag >> (6 * k)) & 63);
+    return d < 0 ? -m : m;
+}
+__device__ __forceinline__ int inv_angle_of(int angle) {
+    constexpr uint64_t kLo = 4096ull | (1638ull << 13) | (910ull << 26) | (630ull << 39);
+    constexpr uint64_t kHi = 482ull | (390ull << 13) | (315ull << 26) | (256ull << 39);
+    const int a = -angle;
+    const int k = a == 2 ? 0 : a == 5 ? 1 : a == 9 ? 2 : a == 13 ? 3 : a == 17 ? 4 : a == 21 ? 5 : a == 26 ? 6 : 7;
+    const uint64_t t = k < 4 ? kLo : kHi;
+    return -(int)((t >> (13 * (k & 3))) & 8191);
+}
+
+// One block's staged samples: orig, and [tl] + up to 2N top / left samples.
+// ntA / nlA are the lengths of topA / leftA (N + 1 .. 2N + 1): an index past
+// the end reads the last sample (intra.py:175-178, D6) -- the clamp, never a
+// read beyond the plane rectangle.
+template <int N>
+struct RdoNBlock {
+    int16_t orig[N * N];
+    int16_t topA[2 * N + 2], leftA[2 * N + 2];
+    int32_t ntA, nlA;
+    int32_t dc;
+    int32_t valid;
+    unsigned long long best;
+};
+
+// Stage block (bx, by) with `nthr` cooperating threads (this one is `tid`).
+template <int N>
+__device__ __forceinline__ void stage_block(RdoNBlock<N>& B, const int16_t* __restrict__ src, int w, int h, int pitch,
+                                            int bx, int by, int tid, int nthr) {
+    const int x = bx * N, y = by * N;
+    for (int e = tid; e < N * N; e += nthr)
+        B.orig[e] = src[(int64_t)(y + e / N) * pitch + x + (e % N)];
+    for (int e = tid; e < 4 * N; e += nthr) {
+        const bool top = e < 2 * N;
+        const int k = top ? e : e - 2 * N;
+        // top row samples x .. x+2N-1 (block.py:38-43) / left column y .. y+2N-1 (block.py:45-50)
+        const bool in = top ? (y > 0 && x + k < w) : (x > 0 && y + k < h);
+        int16_t v = 128;
+        if (in) v = top ? src[(int64_t)(y - 1) * pitch + x + k] : src[(int64_t)(y + k) * pitch + x - 1];
+        (top ? B.topA : B.leftA)[1 + k] = v;
+    }
+    if (tid == 0) {
+        const int16_t tl = (x > 0 && y > 0) ? src[(int64_t)(y - 1) * pitch + x - 1] : (int16_t)128;
+        B.topA[0] = tl;
+        B.leftA[0] = tl;
+        B.ntA = 1 + (y == 0 ? 2 * N : min(2 * N, w - x));
+        B.nlA = 1 + (x == 0 ? 2 * N : min(2 * N, h - y));
+    }
+}
+template <int N>
+__device__ __forceinline__ int32_t block_dc(const RdoNBlock<N>& B) {   // intra.py:61, floor division (D7)
+    int32_t s = 0;
+    for (int k = 1; k <= N; ++k) s += B.topA[k] + B.leftA[k];
+    return (s + N) >> (Log2<N>::v + 1);
+}
+template <int N>
+__device__ __forceinline__ int32_t planar_at(const RdoNBlock<N>& B, int y, int x) {   // intra.py:107-111
+    return ((N - 1 - x) * B.leftA[1 + y] + (x + 1) * B.topA[N] + (N - 1 - y) * B.topA[1 + x] + (y + 1) * B.leftA[N] + N) >>
+           (Log2<N>::v + 1);
+}
+
+// _build_ref_array (intra.py:159-188): logical element i in [-N, 2N] of the
+// reference array of one angular mode.
+struct AngCtx {
+    const int16_t *pri, *sec;
+    int np, ns, angle, inv, next;
+};
+template <int N, class B_>
+__device__ __forceinline__ AngCtx ang_ctx(const B_& B, int mode) {
+    AngCtx a;
+    const bool vert = mode >= 18;
+    a.pri = vert ? B.topA : B.leftA;
+    a.sec = vert ? B.leftA : B.topA;
+    a.np = vert ? B.ntA : B.nlA;
+    a.ns = vert ? B.nlA : B.ntA;
+    a.angle = angle_of(mode);
+    a.inv = a.angle < 0 ? inv_angle_of(a.angle) : 0;
+    a.next = (N * a.angle) >> 5;
+    return a;
+}
+__device__ __forceinline__ int32_t ref_at(const AngCtx& a, int i) {
+    if (i >= 0) return a.pri[i < a.np ? i : a.np - 1];
+    if (a.angle < 0 && i >= a.next) {
+        const int proj = ((i + 1) * a.inv + 128) >> 8;   // (i + 1): D5
+        if (proj < a.ns) return a.sec[proj];
+    }
+    return 0;
+}
+// _project_sample_at (intra.py:191-207) on r0 = ref[idx], r1 = ref[idx + 1]: int16 arithmetic (D8)
+__device__ __forceinline__ int32_t interp(int32_t r0, int32_t r1, int f) {
+    const int32_t v = w16((32 - f) * r0 + f * r1 + 16) >> 5;
+    return f ? v : r0;
+}
+
+__device__ __forceinline__ int32_t clip8(int32_t v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+
+// levels / recon rows of one thread: 16-B pieces when aligned, elements otherwise
+template <int N>
+__device__ __forceinline__ void store_lvl_row(int32_t* row, const int32_t (&l)[N], bool vec) {
+    if (vec) {
+#pragma unroll
+        for (int j = 0; j < N; j += 4) *(int4*)(row + j) = make_int4(l[j], l[j + 1], l[j + 2], l[j + 3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < N; ++j) row[j] = l[j];
+    }
+}
+template <int N>
+__device__ __forceinline__ void store_rec_row(int16_t* row, const uint32_t (&p)[N / 2], bool vec) {
+    if (vec) {
+        if constexpr (N == 4) {
+            *(uint2*)row = make_uint2(p[0], p[1]);       // x0 is a multiple of 4: 8-B aligned
+        } else {
+#pragma unroll
+            for (int j = 0; j < N / 2; j += 4) *(uint4*)(row + 2 * j) = make_uint4(p[j], p[j + 1], p[j + 2], p[j + 3]);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < N; ++j) row[j] = (int16_t)(p[j / 2] >> (16 * (j & 1)));
+    }
+}
+
+__device__ __forceinline__ void plane_offsets(RdoNArgs& a, int nblk) {
+    const int pz = (int)blockIdx.y, gz = pz / a.ppg;
+    const int64_t poff = (int64_t)gz * a.group_stride + (int64_t)(pz - gz * a.ppg) * a.plane_stride;
+    a.src += poff;
+    a.lvl += poff;
+    a.recon += poff;
+    a.modes += (int64_t)pz * nblk;
+    if (a.sse) a.sse += pz;
+}
+
+// ---------------------------------------------------------------------------
+// N = 4: lane = (block slot, mode)
+// ---------------------------------------------------------------------------
+template <bool DST>
+__device__ __forceinline__ void rdo_n_lane(RdoNArgs a) {
+    constexpr int N = 4, S = Log2<N>::v + 5;
+    __shared__ RdoNBlock<N> B[kLaneSlots];
+    __shared__ unsigned long long wg_sse;
+    const int bw = a.w / N, nblk = bw * (a.h / N);
+    plane_offsets(a, nblk);
+    const int t = threadIdx.x;
+    const int slot = t / kModesN, mode = t - slot * kModesN;
+    const int b0 = (int)blockIdx.x * kLaneSlots;
+    {   // 32 threads stage a block
+        const int sb = t / 32, st = t % 32;
+        if (sb < kLaneSlots) {
+            const int b = b0 + sb;
+            if (b < nblk) stage_block<N>(B[sb], a.src, a.w, a.h, a.pitch, b % bw, b / bw, st, 32);
+            if (st == 0) {
+                B[sb].valid = b < nblk;
+                B[sb].best = ULLONG_MAX;
+            }
+        }
+        if (t == 0) wg_sse = 0;
+    }
+    __syncthreads();
+    if (t < kLaneSlots && B[t].valid) B[t].dc = block_dc<N>(B[t]);
+    __syncthreads();
+    const bool active = slot < kLaneSlots && B[slot < kLaneSlots ? slot : 0].valid;
+    const RdoNBlock<N>& L = B[slot < kLaneSlots ? slot : 0];
+    const ChainQ cq = make_chainq(a.qp, a.dq_scale, a.dq_per);
+    int32_t Lv[N][N];
+    uint32_t Rp[N][N / 2];
+    unsigned long long key = ULLONG_MAX;
+    if (active) {
+        int32_t P[N][N];
+        if (mode >= 2) {
+            const AngCtx ac = ang_ctx<N>(L, mode);
+            const bool vert = mode >= 18;
+            int32_t Q[N][N];
+#pragma unroll
+            for (int scan = 0; scan < N; ++scan) {
+                const int proj = (scan + 1) * ac.angle, f = proj & 31;
+#pragma unroll
+                for (int base = 0; base < N; ++base) {
+                    const int i = base + 1 + (proj >> 5);
+                    Q[scan][base] = interp(ref_at(ac, i), ref_at(ac, i + 1), f);
+                }
+            }
+            // pred[y = scan][x = base] for vertical modes, transposed otherwise (intra.py:145-154)
+#pragma unroll
+            for (int y = 0; y < N; ++y)
+#pragma unroll
+                for (int x = 0; x < N; ++x) P[y][x] = vert ? Q[y][x] : Q[x][y];
+        } else {
+#pragma unroll
+            for (int y = 0; y < N; ++y)
+#pragma unroll
+                for (int x = 0; x < N; ++x) P[y][x] = mode == 0 ? planar_at<N>(L, y, x) : L.dc;
+        }
+        uint32_t X[N][N];
+#pragma unroll
+        for (int y = 0; y < N; ++y)
+#pragma unroll
+            for (int x = 0; x < N; ++x) X[y][x] = (uint32_t)w16((int32_t)L.orig[y * N + x] - P[y][x]);   // residual_block
+#pragma unroll
+        for (int j = 0; j < N; ++j) {   // forward pass 1: columns
+            uint32_t x[N], y[N];
+#pragma unroll
+            for (int k = 0; k < N; ++k) x[k] = X[k][j];
+            fwd1d<N, DST, Mul24>(x, y);
+#pragma unroll
+            for (int i = 0; i < N; ++i) X[i][j] = (uint32_t)rshift_round<S>(y[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < N; ++i) {   // forward pass 2: rows, quantize, dequantize
+            uint32_t y[N];
+            fwd1d<N, DST, Mul24>(X[i], y);
+#pragma unroll
+            for (int j = 0; j < N; ++j) {
+                Lv[i][j] = quant_s(rshift_round<S>(y[j]), cq.qs, cq.h_v, cq.hneg_v);
+                X[i][j] = (uint32_t)dequant_s(Lv[i][j], cq);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < N; ++j) {   // inverse pass 1: columns
+            uint32_t yv[N], x[N];
+#pragma unroll
+            for (int k = 0; k < N; ++k) yv[k] = X[k][j];
+            inv1d<N, DST, Mul24>(yv, x);
+#pragma unroll
+            for (int i = 0; i < N; ++i) X[i][j] = (uint32_t)rshift_round<S>(x[i]);
+        }
+        unsigned long long sse = 0;
+#pragma unroll
+        for (int i = 0; i < N; ++i) {   // inverse pass 2: rows, reconstruct, clip, SSE
+            uint32_t x[N];
+            inv1d<N, DST, Mul24>(X[i], x);
+            int32_t rc[N];
+#pragma unroll
+            for (int j = 0; j < N; ++j) {
+                rc[j] = clip8(w16(P[i][j] + w16(rshift_round<S>(x[j]))));
+                const int32_t d = w16((int32_t)L.orig[i * N + j] - rc[j]);
+                sse += (unsigned long long)(uint32_t)(d * d);
+            }
+#pragma unroll
+            for (int j = 0; j < N; j += 2) Rp[i][j / 2] = (uint32_t)rc[j] | ((uint32_t)rc[j + 1] << 16);
+        }
+        key = (sse << 6) | (unsigned long long)mode;
+        atomicMin(&B[slot].best, key);
+    }
+    __syncthreads();
+    if (active && key == L.best) {
+        const int b = b0 + slot;
+        const int by = b / bw, bx = b - by * bw;
+        a.modes[b] = (uint8_t)mode;
+        atomicAdd(&wg_sse, key >> 6);
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            const int64_t o = (int64_t)(by * N + i) * a.pitch + bx * N;
+            store_lvl_row<N>(a.lvl + o, Lv[i], a.vec_out);
+            store_rec_row<N>(a.recon + o, Rp[i], a.vec_out);
+        }
+    }
+    __syncthreads();
+    if (a.sse && t == 0) atomicAdd(a.sse, wg_sse);   // once per workgroup
+}
+
+// ---------------------------------------------------------------------------
+// N = 16 / 32: N lanes per (block, mode) chain
+// ---------------------------------------------------------------------------
+// Between an LDS write and another lane's read inside one chain: the chain's
+// lanes are in one wave, whose LDS instructions execute in program order, so
+// only the compiler has to keep the order.
+__device__ __forceinline__ void chain_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <int N>
+__device__ __forceinline__ void rdo_n_tile(RdoNArgs a) {
+    constexpr int BPW = 32 / N;                 // blocks per workgroup
+    constexpr int NC = kChains * BPW;           // chains per workgroup
+    constexpr int NT = NC * N;                  // 224 threads
+    constexpr int P = N + 1, S = Log2<N>::v + 5;
+    __shared__ RdoNBlock<N> B[BPW];
+    __shared__ int32_t tile[NC][N][P];
+    __shared__ int16_t refs[NC][3 * N + 2];
+    const int bw = a.w / N, nblk = bw * (a.h / N);
+    plane_offsets(a, nblk);
+    const int tid = threadIdx.x;
+    const int ci = tid / N, t = tid % N;
+    const int blk = ci / kChains, c = ci - blk * kChains;
+    const int b0 = (int)blockIdx.x * BPW;
+    for (int k = 0; k < BPW; ++k) {
+        const int b = b0 + k;
+        if (b < nblk) stage_block<N>(B[k], a.src, a.w, a.h, a.pitch, b % bw, b / bw, tid, NT);
+        if (tid == 0) {
+            B[k].valid = b < nblk;
+            B[k].best = ULLONG_MAX;
+        }
+    }
+    __syncthreads();
+    if (tid < BPW && B[tid].valid) B[tid].dc = block_dc<N>(B[tid]);
+    __syncthreads();
+    const RdoNBlock<N>& L = B[blk];
+    const bool on = L.valid != 0;
+    const ChainQ cq = make_chainq(a.qp, a.dq_scale, a.dq_per);
+    const int b = b0 + blk;
+    const int y0 = (b / bw) * N, x0 = (b % bw) * N;
+    int16_t* rf = refs[ci];
+
+    for (int r = 0; r <= kModesN / kChains; ++r) {
+        const bool emit = r == kModesN / kChains;      // the winner's round
+        if (emit) {
+            __syncthreads();                           // every chain's key is in L.best
+            if (tid == 0 && a.sse) {
+                unsigned long long s = 0;
+                for (int k = 0; k < BPW; ++k)
+                    if (B[k].valid) s += B[k].best >> 6;
+                atomicAdd(a.sse, s);                   // once per workgroup
+            }
+            if (!on || c != 0) return;
+        }
+        if (!on) continue;
+        const int mode = emit ? (int)(L.best & 63) : r * kChains + c;
+        int angle = 0;
+        const bool vert = mode >= 18;
+        if (mode >= 2) {
+            const AngCtx ac = ang_ctx<N>(L, mode);
+            angle = ac.angle;
+            for (int i = t; i < 3 * N + 2; i += N) rf[i] = i <= 3 * N ? (int16_t)ref_at(ac, i - N) : (int16_t)0;
+        }
+        chain_sync();
+        auto pred_at = [&](int y, int x) -> int32_t {
+            if (mode == 0) return planar_at<N>(L, y, x);
+            if (mode == 1) return L.dc;
+            const int base = vert ? x : y, scan = vert ? y : x;
+            const int proj = (scan + 1) * angle;
+            const int16_t* rp = rf + N + base + 1 + (proj >> 5);
+            return interp(rp[0], rp[1], proj & 31);
+        };
+        uint32_t v[N], q[N];
+        // forward pass 1 on column t of the residual
+#pragma unroll
+        for (int k = 0; k < N; ++k) v[k] = (uint32_t)w16((int32_t)L.orig[k * N + t] - pred_at(k, t));
+        fwd1d<N, false, Mul24>(v, q);
+#pragma unroll
+        for (int i = 0; i < N; ++i) tile[ci][i][t] = rshift_round<S>(q[i]);
+        chain_sync();
+        // forward pass 2 on row t, quantize, dequantize (row t is this lane's own)
+#pragma unroll
+        for (int k = 0; k < N; ++k) v[k] = (uint32_t)tile[ci][t][k];
+        fwd1d<N, false, Mul24>(v, q);
+        {
+            int32_t l[N];
+#pragma unroll
+            for (int j = 0; j < N; ++j) {
+                l[j] = quant_s(rshift_round<S>(q[j]), cq.qs, cq.h_v, cq.hneg_v);
+                tile[ci][t][j] = dequant_s(l[j], cq);
+            }
+            if (emit) store_lvl_row<N>(a.lvl + (int64_t)(y0 + t) * a.pitch + x0, l, a.vec_out);
+        }
+        chain_sync();
+        // inverse pass 1 on column t (this lane's own column)
+#pragma unroll
+        for (int k = 0; k < N; ++k) v[k] = (uint32_t)tile[ci][k][t];
+        inv1d<N, false, Mul24>(v, q);
+#pragma unroll
+        for (int i = 0; i < N; ++i) tile[ci][i][t] = rshift_round<S>(q[i]);
+        chain_sync();
+        // inverse pass 2 on row t, reconstruct, clip, SSE
+#pragma unroll
+        for (int k = 0; k < N; ++k) v[k] = (uint32_t)tile[ci][t][k];
+        inv1d<N, false, Mul24>(v, q);
+        unsigned long long sse = 0;
+        uint32_t rcp[N / 2];
+#pragma unroll
+        for (int j = 0; j < N; j += 2) {
+            int32_t rc2[2];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                rc2[u] = clip8(w16(pred_at(t, j + u) + w16(rshift_round<S>(q[j + u]))));
+                const int32_t d = w16((int32_t)L.orig[t * N + j + u] - rc2[u]);
+                sse += (unsigned long long)(uint32_t)(d * d);
+            }
+            rcp[j / 2] = (uint32_t)rc2[0] | ((uint32_t)rc2[1] << 16);
+        }
+        if (emit) {
+            store_rec_row<N>(a.recon + (int64_t)(y0 + t) * a.pitch + x0, rcp, a.vec_out);
+            if (t == 0) a.modes[b] = (uint8_t)mode;
+            return;
+        }
+        // the chain's SSE: sum over its N lanes (an aligned group of N lanes of the wave)
+#pragma unroll
+        for (int m = N / 2; m >= 1; m >>= 1) sse += __shfl_xor(sse, m);
+        if (t == 0) atomicMin(&B[blk].best, (sse << 6) | (unsigned long long)mode);
+        chain_sync();   // refs / tile are rewritten by the next round
+    }
+}
+
+template <int N, bool DST>
+__global__ void __launch_bounds__(N == 4 ? 256 : 224) k_intra_rdo_n(RdoNArgs a) {
+    if constexpr (N == 4) rdo_n_lane<DST>(a); else rdo_n_tile<N>(a);
+}
+
+void split_qp(int qp, int log2n, QuantParams* q, int* per, int* rem) {
+    *per = qp / 6;
+    *rem = qp % 6;
+    q->shift = 14 + *per + log2n;
+    q->mf = quant_scale(*rem);
+    q->off = (uint32_t)((1ull << q->shift) / 3);   // intra rounding (quant.py:66-69)
+}
+
+}  // namespace
+}  // namespace nh
+
+using namespace nh;
+
+extern "C" int nh_intra_rdo_planes_n(const int16_t* d_src, const nh_plane_set* sets, int nsets, int block_size,
+                                     int use_dst, int qp, uint8_t* d_modes, int32_t* d_lvl, int16_t* d_recon,
+                                     int64_t* d_sse, void* stream) {
+    if (!d_src || !sets || !d_modes || !d_lvl || !d_recon) {
+        set_error("nh_intra_rdo_planes_n: null argument");
+        return NH_EARG;
+    }
+    if (block_size != 4 && block_size != 8 && block_size != 16 && block_size != 32) {
+        set_error("nh_intra_rdo_planes_n: block_size must be 4, 8, 16 or 32");
+        return NH_EARG;
+    }
+    if (use_dst && block_size != 4) {
+        set_error("nh_intra_rdo_planes_n: use_dst needs block_size 4 (transform.py:138-141)");
+        return NH_EARG;
+    }
+    if (qp < 0 || qp > 51) {
+        set_error("nh_intra_rdo_planes_n: qp outside 0..51");
+        return NH_EARG;
+    }
+    if (nsets < 1 || nsets > NH_MAX_PLANE_SETS) {
+        set_error("nh_intra_rdo_planes_n: nsets outside 1..8");
+        return NH_EARG;
+    }
+    for (int k = 0; k < nsets; ++k) {
+        const nh_plane_set& S = sets[k];
+        const int64_t planes = (int64_t)S.planes_per_group * S.num_groups;
+        if (S.width < 0 || S.height < 0 || S.pitch < S.width || S.planes_per_group < 1 || S.num_groups < 0 ||
+            planes > 65535 || S.base < 0 || S.plane_stride < 0 || S.group_stride < 0) {
+            set_error("nh_intra_rdo_planes_n: bad plane set");
+            return NH_EARG;
+        }
+    }
+    if (block_size == 8) return nh_intra_rdo_planes(d_src, sets, nsets, qp, d_modes, d_lvl, d_recon, d_sse, stream);
+
+    const int N = block_size, log2n = N == 4 ? 2 : N == 16 ? 4 : 5;
+    RdoNArgs a{};
+    int per, rem;
+    split_qp(qp, log2n, &a.qp, &per, &rem);
+    a.dq_scale = dequant_scale(rem);
+    a.dq_per = per;
+    const hipStream_t s = as_stream(stream);
+    int64_t moff = 0, soff = 0;
+    for (int k = 0; k < nsets; ++k) {
+        const nh_plane_set& S = sets[k];
+        const int64_t planes = (int64_t)S.planes_per_group * S.num_groups;
+        const int nblk = (S.width / N) * (S.height / N);
+        if (nblk && planes) {
+            a.src = d_src + S.base;
+            a.lvl = d_lvl + S.base;
+            a.recon = d_recon + S.base;
+            a.modes = d_modes + moff;
+            a.sse = d_sse ? (unsigned long long*)(d_sse + soff) : nullptr;
+            a.w = S.width;
+            a.h = S.height;
+            a.pitch = S.pitch;
+            a.vec_out = !(S.pitch & 7) && !((S.base | S.plane_stride | S.group_stride) & 7) &&
+                        !((uintptr_t)d_lvl & 15) && !((uintptr_t)d_recon & 15);
+            a.group_stride = S.group_stride;
+            a.plane_stride = S.plane_stride;
+            a.ppg = S.planes_per_group;
+            const unsigned py = (unsigned)planes;
+            if (N == 4) {
+                const dim3 grid((unsigned)((nblk + kLaneSlots - 1) / kLaneSlots), py);
+                if (use_dst) k_intra_rdo_n<4, true><<<grid, 256, 0, s>>>(a);
+                else k_intra_rdo_n<4, false><<<grid, 256, 0, s>>>(a);
+            } else if (N == 16) {
+                k_intra_rdo_n<16, false><<<dim3((unsigned)((nblk + 1) / 2), py), 224, 0, s>>>(a);
+            } else {
+                k_intra_rdo_n<32, false><<<dim3((unsigned)nblk, py), 224, 0, s>>>(a);
+            }
+            NH_HIP(hipGetLastError());
+        }
+        moff += planes * nblk;
+        soff += planes;
+    }
+    return NH_OK;
+}

@@ -8,6 +8,7 @@ launch the gfx950 kernels through the C ABI on the tensor's current stream.
   yuv420_plane_sets   -- nh_plane_set descriptors for a stream of YUV420 frames
   fwd_transform_batch / inv_transform_batch / quant_batch / dequant_batch
   intra_rdo_plane     -- config 3: 35-mode RDO per 8x8 block of a plane; intra_rdo_planes: over plane sets
+  intra_rdo_planes_n  -- config 3 at N = 4 (DST / DCT), 8, 16, 32 over plane sets; intra_rdo_plane_n: one plane
   intra_rdo_closed    -- config 3 in closed loop (row wavefront); _yuv420_stream: in batches, several in flight
   dequant_inv8x8      -- decoder stage R: dequantise + inverse 8x8 DCT over plane sets (fwd8x8_quant's mirror)
   intra_decode_closed -- the decoder of intra_rdo_closed: modes + levels -> its reconstruction
@@ -301,6 +302,63 @@ def intra_rdo_planes(src, sets: Sequence[PlaneSet], qp: int = 32, lvl=None, rec=
                                           rec.data_ptr(), sse.data_ptr(), C.c_void_p(_stream(stream, dev))),
           "intra_rdo_planes")
     return modes[:nmodes], lvl, rec, sse[:nplanes]
+
+
+def intra_rdo_planes_n(src, sets: Sequence[PlaneSet], block_size: int, qp: int = 32, use_dst: bool = False,
+                       lvl=None, rec=None, stream=None):
+    """Config 3 at block size N = ``block_size`` in {4, 8, 16, 32}
+    over every plane of ``sets``: the best of the 35 intra modes per full NxN
+    block, open loop.  ``use_dst`` (N = 4 only) selects the 4x4 DST-VII.  Returns
+    (modes uint8 [sum of per-plane (h/N)*(w/N), set order], lvl int32, recon int16
+    (source layout; samples outside full blocks keep the caller's contents), sse
+    int64 per plane).  A QP outside 0..51 raises ValueError (it is not clamped);
+    N = 8 runs the ``intra_rdo_planes`` kernels."""
+    torch = _torch()
+    _need(src, torch.int16, "intra_rdo_planes_n(src)")
+    n = int(block_size)
+    if n not in (4, 8, 16, 32):
+        raise ValueError(f"intra_rdo_planes_n: block_size must be 4, 8, 16 or 32, got {block_size}")
+    sets_fit(sets, src.numel(), "intra_rdo_planes_n")
+    nmodes = sum((s.width // n) * (s.height // n) * s.planes_per_group * s.num_groups for s in sets)
+    nplanes = sum(s.planes_per_group * s.num_groups for s in sets)
+    dev = src.device
+    if lvl is None:
+        lvl = torch.zeros(src.shape, dtype=torch.int32, device=dev)
+    if rec is None:
+        rec = torch.zeros(src.shape, dtype=torch.int16, device=dev)
+    _need(lvl, torch.int32, "intra_rdo_planes_n(lvl)")
+    _need(rec, torch.int16, "intra_rdo_planes_n(rec)")
+    if lvl.numel() < src.numel() or rec.numel() < src.numel():
+        raise ValueError("intra_rdo_planes_n: lvl / rec smaller than src")
+    modes = torch.zeros(max(1, nmodes), dtype=torch.uint8, device=dev)
+    sse = torch.zeros(max(1, nplanes), dtype=torch.int64, device=dev)
+    arr = (PlaneSet * max(1, len(sets)))(*sets)
+    check(_lib.load().nh_intra_rdo_planes_n(src.data_ptr(), arr, len(sets), n, int(bool(use_dst)), int(qp),
+                                            modes.data_ptr(), lvl.data_ptr(), rec.data_ptr(), sse.data_ptr(),
+                                            C.c_void_p(_stream(stream, dev))), "intra_rdo_planes_n")
+    return modes[:nmodes], lvl, rec, sse[:nplanes]
+
+
+def intra_rdo_plane_n(src, block_size: int, qp: int = 32, use_dst: bool = False, pitch: int | None = None,
+                      stream=None):
+    """``intra_rdo_planes_n`` on one int16 plane (H, W) whose rows are ``pitch`` (default
+    W) samples apart: (modes u8 (H/N, W/N), levels int32 (H, W), recon int16 (H, W),
+    sse int64 (1,))."""
+    torch = _torch()
+    _need(src, torch.int16, "intra_rdo_plane_n")
+    h, w = src.shape
+    p = int(pitch or w)
+    if p != w:   # rows of the (H, W) tensor re-spaced: run on a pitched copy, return (H, W) views
+        if p < w:
+            raise ValueError("intra_rdo_plane_n: pitch < width")
+        buf = torch.zeros((h, p), dtype=torch.int16, device=src.device)
+        buf[:, :w] = src
+        modes, lvl, rec, sse = intra_rdo_planes_n(buf, [plane_set(0, w, h, p)], block_size, qp, use_dst, stream=stream)
+        lvl, rec = lvl[:, :w], rec[:, :w]
+    else:
+        modes, lvl, rec, sse = intra_rdo_planes_n(src, [plane_set(0, w, h, w)], block_size, qp, use_dst, stream=stream)
+    n = int(block_size)
+    return modes.reshape(h // n, w // n), lvl, rec, sse
 
 
 def intra_rdo_closed(src, sets: Sequence[PlaneSet], qp: int = 32, lvl=None, rec=None, stream=None):
