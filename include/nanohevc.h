@@ -355,6 +355,31 @@ int nh_intra_rdo_planes_closed(const int16_t* d_src, const nh_plane_set* sets, i
                                void* d_work, void* stream);
 int nh_intra_rdo_closed_status(const void* d_work, int* status, void* stream);
 
+/* Config 3, CLOSED loop, at every HEVC block size: the closed
+ * loop above per full NxN block, N = block_size in {4, 8, 16, 32}; use_dst
+ * selects the 4x4 DST-VII and is allowed only with block_size 4.  Angular
+ * references: [tl] + 2N top samples of the reconstruction (truncated at the
+ * plane's right edge, 0 past the last full block) and [tl] + the N
+ * reconstructed left samples, both extended by the replicate-last rule.  Modes,
+ * chain, cost and ties as nh_intra_rdo_planes_n.  d_modes: (h/N)*(w/N) u8 per
+ * plane, planes in set order; d_lvl (int32): only samples of full blocks
+ * written; d_recon (int16): 0 outside full blocks; d_sse: one int64 per plane,
+ * ACCUMULATED.  d_work: nh_intra_rdo_closed_n_workspace_bytes() bytes of device
+ * memory, 8-B aligned (zeroed by the call); the status word is read with
+ * nh_intra_rdo_closed_status (0 ok, 1 a wavefront wait did not complete).
+ * A worker per block row (a wave at N = 4, a 224-lane workgroup at N = 16 / 32).
+ * Returns NH_EARG on the host, before any HIP call (text in nh_last_error), for
+ * the cases nh_intra_rdo_planes_n refuses; the workspace-size call returns a
+ * negative value for them.  block_size 8 is checked, then forwarded to
+ * nh_intra_rdo_planes_closed / nh_intra_rdo_closed_workspace_bytes.  16-byte
+ * row stores when base, pitch and strides are multiples of 8 elements and both
+ * output buffers are 16-B aligned, element stores otherwise -- same results. */
+int64_t nh_intra_rdo_closed_n_workspace_bytes(const nh_plane_set* sets, int nsets, int block_size);
+int nh_intra_rdo_planes_closed_n(const int16_t* d_src, const nh_plane_set* sets, int nsets,
+                                 int block_size, int use_dst, int qp, uint8_t* d_modes,
+                                 int32_t* d_lvl, int16_t* d_recon, int64_t* d_sse,
+                                 void* d_work, void* stream);
+
 /* ---- Closed-loop intra DECODER: modes + levels -> recon ----
  * Stage R: res = inverse_transform(dequantize_block(level, qp)).astype(int16)
  * (quant.py:82-123, transform.py:199-238, int32 wrap-around included) over every

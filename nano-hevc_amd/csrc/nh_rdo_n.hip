@@ -28,10 +28,18 @@
 // Multiplies: the chain is k_tu_process's, whose 24-bit multiplies are exact for
 // every int16 residual at every QP and size; tools/rdo_n_bounds.py enumerates the
 // operand bounds for the transforms used here (tests/test_rdo_n_host.py).
+//
+// The CLOSED loop at the same sizes (second half of the
+// file): the same chains, neighbours from the reconstruction, on the row
+// wavefront of the N = 8 closed loop.  Its residual is int16 whatever the
+// prediction, so the operand bounds above hold for it as they are.
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <climits>
+#include <string>
 #include "nh_common.hpp"
 #include "nh_internal.hpp"
+#include "nh_closed_ticket.hpp"
 
 namespace nh {
 namespace {
@@ -196,12 +204,95 @@ __device__ __forceinline__ void plane_offsets(RdoNArgs& a, int nblk) {
     if (a.sse) a.sse += pz;
 }
 
+// One 4x4 (block, mode) chain of one lane, the block in registers: prediction from the staged
+// neighbours, residual -> transform -> quantize -> dequantize -> inverse -> reconstruct -> clip.
+// Lv: the levels, Rp: the recon as int16 pairs, both row-major; returns the SSE.
+template <bool DST>
+__device__ __forceinline__ unsigned long long lane_chain4(const RdoNBlock<4>& L, int mode, const ChainQ& cq,
+                                                          int32_t (&Lv)[4][4], uint32_t (&Rp)[4][2]) {
+    constexpr int N = 4, S = Log2<N>::v + 5;
+    int32_t P[N][N];
+    if (mode >= 2) {
+        const AngCtx ac = ang_ctx<N>(L, mode);
+        const bool vert = mode >= 18;
+        int32_t Q[N][N];
+#pragma unroll
+        for (int scan = 0; scan < N; ++scan) {
+            const int proj = (scan + 1) * ac.angle, f = proj & 31;
+#pragma unroll
+            for (int base = 0; base < N; ++base) {
+                const int i = base + 1 + (proj >> 5);
+                Q[scan][base] = interp(ref_at(ac, i), ref_at(ac, i + 1), f);
+            }
+        }
+        // pred[y = scan][x = base] for vertical modes, transposed otherwise (intra.py:145-154)
+#pragma unroll
+        for (int y = 0; y < N; ++y)
+#pragma unroll
+            for (int x = 0; x < N; ++x) P[y][x] = vert ? Q[y][x] : Q[x][y];
+    } else {
+#pragma unroll
+        for (int y = 0; y < N; ++y)
+#pragma unroll
+            for (int x = 0; x < N; ++x) P[y][x] = mode == 0 ? planar_at<N>(L, y, x) : L.dc;
+    }
+    uint32_t X[N][N];
+#pragma unroll
+    for (int y = 0; y < N; ++y)
+#pragma unroll
+        for (int x = 0; x < N; ++x) X[y][x] = (uint32_t)w16((int32_t)L.orig[y * N + x] - P[y][x]);   // residual_block
+#pragma unroll
+    for (int j = 0; j < N; ++j) {   // forward pass 1: columns
+        uint32_t x[N], y[N];
+#pragma unroll
+        for (int k = 0; k < N; ++k) x[k] = X[k][j];
+        fwd1d<N, DST, Mul24>(x, y);
+#pragma unroll
+        for (int i = 0; i < N; ++i) X[i][j] = (uint32_t)rshift_round<S>(y[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) {   // forward pass 2: rows, quantize, dequantize
+        uint32_t y[N];
+        fwd1d<N, DST, Mul24>(X[i], y);
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            Lv[i][j] = quant_s(rshift_round<S>(y[j]), cq.qs, cq.h_v, cq.hneg_v);
+            X[i][j] = (uint32_t)dequant_s(Lv[i][j], cq);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j) {   // inverse pass 1: columns
+        uint32_t yv[N], x[N];
+#pragma unroll
+        for (int k = 0; k < N; ++k) yv[k] = X[k][j];
+        inv1d<N, DST, Mul24>(yv, x);
+#pragma unroll
+        for (int i = 0; i < N; ++i) X[i][j] = (uint32_t)rshift_round<S>(x[i]);
+    }
+    unsigned long long sse = 0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {   // inverse pass 2: rows, reconstruct, clip, SSE
+        uint32_t x[N];
+        inv1d<N, DST, Mul24>(X[i], x);
+        int32_t rc[N];
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            rc[j] = clip8(w16(P[i][j] + w16(rshift_round<S>(x[j]))));
+            const int32_t d = w16((int32_t)L.orig[i * N + j] - rc[j]);
+            sse += (unsigned long long)(uint32_t)(d * d);
+        }
+#pragma unroll
+        for (int j = 0; j < N; j += 2) Rp[i][j / 2] = (uint32_t)rc[j] | ((uint32_t)rc[j + 1] << 16);
+    }
+    return sse;
+}
+
 // ---------------------------------------------------------------------------
 // N = 4: lane = (block slot, mode)
 // ---------------------------------------------------------------------------
 template <bool DST>
 __device__ __forceinline__ void rdo_n_lane(RdoNArgs a) {
-    constexpr int N = 4, S = Log2<N>::v + 5;
+    constexpr int N = 4;
     __shared__ RdoNBlock<N> B[kLaneSlots];
     __shared__ unsigned long long wg_sse;
     const int bw = a.w / N, nblk = bw * (a.h / N);
@@ -231,80 +322,7 @@ __device__ __forceinline__ void rdo_n_lane(RdoNArgs a) {
     uint32_t Rp[N][N / 2];
     unsigned long long key = ULLONG_MAX;
     if (active) {
-        int32_t P[N][N];
-        if (mode >= 2) {
-            const AngCtx ac = ang_ctx<N>(L, mode);
-            const bool vert = mode >= 18;
-            int32_t Q[N][N];
-#pragma unroll
-            for (int scan = 0; scan < N; ++scan) {
-                const int proj = (scan + 1) * ac.angle, f = proj & 31;
-#pragma unroll
-                for (int base = 0; base < N; ++base) {
-                    const int i = base + 1 + (proj >> 5);
-                    Q[scan][base] = interp(ref_at(ac, i), ref_at(ac, i + 1), f);
-                }
-            }
-            // pred[y = scan][x = base] for vertical modes, transposed otherwise (intra.py:145-154)
-#pragma unroll
-            for (int y = 0; y < N; ++y)
-#pragma unroll
-                for (int x = 0; x < N; ++x) P[y][x] = vert ? Q[y][x] : Q[x][y];
-        } else {
-#pragma unroll
-            for (int y = 0; y < N; ++y)
-#pragma unroll
-                for (int x = 0; x < N; ++x) P[y][x] = mode == 0 ? planar_at<N>(L, y, x) : L.dc;
-        }
-        uint32_t X[N][N];
-#pragma unroll
-        for (int y = 0; y < N; ++y)
-#pragma unroll
-            for (int x = 0; x < N; ++x) X[y][x] = (uint32_t)w16((int32_t)L.orig[y * N + x] - P[y][x]);   // residual_block
-#pragma unroll
-        for (int j = 0; j < N; ++j) {   // forward pass 1: columns
-            uint32_t x[N], y[N];
-#pragma unroll
-            for (int k = 0; k < N; ++k) x[k] = X[k][j];
-            fwd1d<N, DST, Mul24>(x, y);
-#pragma unroll
-            for (int i = 0; i < N; ++i) X[i][j] = (uint32_t)rshift_round<S>(y[i]);
-        }
-#pragma unroll
-        for (int i = 0; i < N; ++i) {   // forward pass 2: rows, quantize, dequantize
-            uint32_t y[N];
-            fwd1d<N, DST, Mul24>(X[i], y);
-#pragma unroll
-            for (int j = 0; j < N; ++j) {
-                Lv[i][j] = quant_s(rshift_round<S>(y[j]), cq.qs, cq.h_v, cq.hneg_v);
-                X[i][j] = (uint32_t)dequant_s(Lv[i][j], cq);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < N; ++j) {   // inverse pass 1: columns
-            uint32_t yv[N], x[N];
-#pragma unroll
-            for (int k = 0; k < N; ++k) yv[k] = X[k][j];
-            inv1d<N, DST, Mul24>(yv, x);
-#pragma unroll
-            for (int i = 0; i < N; ++i) X[i][j] = (uint32_t)rshift_round<S>(x[i]);
-        }
-        unsigned long long sse = 0;
-#pragma unroll
-        for (int i = 0; i < N; ++i) {   // inverse pass 2: rows, reconstruct, clip, SSE
-            uint32_t x[N];
-            inv1d<N, DST, Mul24>(X[i], x);
-            int32_t rc[N];
-#pragma unroll
-            for (int j = 0; j < N; ++j) {
-                rc[j] = clip8(w16(P[i][j] + w16(rshift_round<S>(x[j]))));
-                const int32_t d = w16((int32_t)L.orig[i * N + j] - rc[j]);
-                sse += (unsigned long long)(uint32_t)(d * d);
-            }
-#pragma unroll
-            for (int j = 0; j < N; j += 2) Rp[i][j / 2] = (uint32_t)rc[j] | ((uint32_t)rc[j + 1] << 16);
-        }
-        key = (sse << 6) | (unsigned long long)mode;
+        key = (lane_chain4<DST>(L, mode, cq, Lv, Rp) << 6) | (unsigned long long)mode;
         atomicMin(&B[slot].best, key);
     }
     __syncthreads();
@@ -336,12 +354,85 @@ __device__ __forceinline__ void chain_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// One (block, mode) chain on the N lanes of a chain: lane t does column t, then row t, through
+// the chain's LDS tile (pitch N + 1); rf: the chain's 3N + 2 angular reference samples.  Returns
+// the SSE of row t; rcp: row t of the recon as int16 pairs.  lvl_row (the winner's round): where
+// lane t stores row t of the levels, or null.
+template <int N>
+__device__ __forceinline__ unsigned long long tile_chain(const RdoNBlock<N>& L, int mode, int t, int32_t (*tile)[N + 1],
+                                                         int16_t* rf, const ChainQ& cq, int32_t* lvl_row, bool vec,
+                                                         uint32_t (&rcp)[N / 2]) {
+    constexpr int S = Log2<N>::v + 5;
+    int angle = 0;
+    const bool vert = mode >= 18;
+    if (mode >= 2) {
+        const AngCtx ac = ang_ctx<N>(L, mode);
+        angle = ac.angle;
+        for (int i = t; i < 3 * N + 2; i += N) rf[i] = i <= 3 * N ? (int16_t)ref_at(ac, i - N) : (int16_t)0;
+    }
+    chain_sync();
+    auto pred_at = [&](int y, int x) -> int32_t {
+        if (mode == 0) return planar_at<N>(L, y, x);
+        if (mode == 1) return L.dc;
+        const int base = vert ? x : y, scan = vert ? y : x;
+        const int proj = (scan + 1) * angle;
+        const int16_t* rp = rf + N + base + 1 + (proj >> 5);
+        return interp(rp[0], rp[1], proj & 31);
+    };
+    uint32_t v[N], q[N];
+    // forward pass 1 on column t of the residual
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = (uint32_t)w16((int32_t)L.orig[k * N + t] - pred_at(k, t));
+    fwd1d<N, false, Mul24>(v, q);
+#pragma unroll
+    for (int i = 0; i < N; ++i) tile[i][t] = rshift_round<S>(q[i]);
+    chain_sync();
+    // forward pass 2 on row t, quantize, dequantize (row t is this lane's own)
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = (uint32_t)tile[t][k];
+    fwd1d<N, false, Mul24>(v, q);
+    {
+        int32_t l[N];
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            l[j] = quant_s(rshift_round<S>(q[j]), cq.qs, cq.h_v, cq.hneg_v);
+            tile[t][j] = dequant_s(l[j], cq);
+        }
+        if (lvl_row) store_lvl_row<N>(lvl_row, l, vec);
+    }
+    chain_sync();
+    // inverse pass 1 on column t (this lane's own column)
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = (uint32_t)tile[k][t];
+    inv1d<N, false, Mul24>(v, q);
+#pragma unroll
+    for (int i = 0; i < N; ++i) tile[i][t] = rshift_round<S>(q[i]);
+    chain_sync();
+    // inverse pass 2 on row t, reconstruct, clip, SSE
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = (uint32_t)tile[t][k];
+    inv1d<N, false, Mul24>(v, q);
+    unsigned long long sse = 0;
+#pragma unroll
+    for (int j = 0; j < N; j += 2) {
+        int32_t rc2[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            rc2[u] = clip8(w16(pred_at(t, j + u) + w16(rshift_round<S>(q[j + u]))));
+            const int32_t d = w16((int32_t)L.orig[t * N + j + u] - rc2[u]);
+            sse += (unsigned long long)(uint32_t)(d * d);
+        }
+        rcp[j / 2] = (uint32_t)rc2[0] | ((uint32_t)rc2[1] << 16);
+    }
+    return sse;
+}
+
 template <int N>
 __device__ __forceinline__ void rdo_n_tile(RdoNArgs a) {
     constexpr int BPW = 32 / N;                 // blocks per workgroup
     constexpr int NC = kChains * BPW;           // chains per workgroup
     constexpr int NT = NC * N;                  // 224 threads
-    constexpr int P = N + 1, S = Log2<N>::v + 5;
+    constexpr int P = N + 1;
     __shared__ RdoNBlock<N> B[BPW];
     __shared__ int32_t tile[NC][N][P];
     __shared__ int16_t refs[NC][3 * N + 2];
@@ -383,68 +474,9 @@ __device__ __forceinline__ void rdo_n_tile(RdoNArgs a) {
         }
         if (!on) continue;
         const int mode = emit ? (int)(L.best & 63) : r * kChains + c;
-        int angle = 0;
-        const bool vert = mode >= 18;
-        if (mode >= 2) {
-            const AngCtx ac = ang_ctx<N>(L, mode);
-            angle = ac.angle;
-            for (int i = t; i < 3 * N + 2; i += N) rf[i] = i <= 3 * N ? (int16_t)ref_at(ac, i - N) : (int16_t)0;
-        }
-        chain_sync();
-        auto pred_at = [&](int y, int x) -> int32_t {
-            if (mode == 0) return planar_at<N>(L, y, x);
-            if (mode == 1) return L.dc;
-            const int base = vert ? x : y, scan = vert ? y : x;
-            const int proj = (scan + 1) * angle;
-            const int16_t* rp = rf + N + base + 1 + (proj >> 5);
-            return interp(rp[0], rp[1], proj & 31);
-        };
-        uint32_t v[N], q[N];
-        // forward pass 1 on column t of the residual
-#pragma unroll
-        for (int k = 0; k < N; ++k) v[k] = (uint32_t)w16((int32_t)L.orig[k * N + t] - pred_at(k, t));
-        fwd1d<N, false, Mul24>(v, q);
-#pragma unroll
-        for (int i = 0; i < N; ++i) tile[ci][i][t] = rshift_round<S>(q[i]);
-        chain_sync();
-        // forward pass 2 on row t, quantize, dequantize (row t is this lane's own)
-#pragma unroll
-        for (int k = 0; k < N; ++k) v[k] = (uint32_t)tile[ci][t][k];
-        fwd1d<N, false, Mul24>(v, q);
-        {
-            int32_t l[N];
-#pragma unroll
-            for (int j = 0; j < N; ++j) {
-                l[j] = quant_s(rshift_round<S>(q[j]), cq.qs, cq.h_v, cq.hneg_v);
-                tile[ci][t][j] = dequant_s(l[j], cq);
-            }
-            if (emit) store_lvl_row<N>(a.lvl + (int64_t)(y0 + t) * a.pitch + x0, l, a.vec_out);
-        }
-        chain_sync();
-        // inverse pass 1 on column t (this lane's own column)
-#pragma unroll
-        for (int k = 0; k < N; ++k) v[k] = (uint32_t)tile[ci][k][t];
-        inv1d<N, false, Mul24>(v, q);
-#pragma unroll
-        for (int i = 0; i < N; ++i) tile[ci][i][t] = rshift_round<S>(q[i]);
-        chain_sync();
-        // inverse pass 2 on row t, reconstruct, clip, SSE
-#pragma unroll
-        for (int k = 0; k < N; ++k) v[k] = (uint32_t)tile[ci][t][k];
-        inv1d<N, false, Mul24>(v, q);
-        unsigned long long sse = 0;
         uint32_t rcp[N / 2];
-#pragma unroll
-        for (int j = 0; j < N; j += 2) {
-            int32_t rc2[2];
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                rc2[u] = clip8(w16(pred_at(t, j + u) + w16(rshift_round<S>(q[j + u]))));
-                const int32_t d = w16((int32_t)L.orig[t * N + j + u] - rc2[u]);
-                sse += (unsigned long long)(uint32_t)(d * d);
-            }
-            rcp[j / 2] = (uint32_t)rc2[0] | ((uint32_t)rc2[1] << 16);
-        }
+        unsigned long long sse = tile_chain<N>(L, mode, t, tile[ci], rf, cq,
+                                               emit ? a.lvl + (int64_t)(y0 + t) * a.pitch + x0 : nullptr, a.vec_out, rcp);
         if (emit) {
             store_rec_row<N>(a.recon + (int64_t)(y0 + t) * a.pitch + x0, rcp, a.vec_out);
             if (t == 0) a.modes[b] = (uint8_t)mode;
@@ -471,6 +503,405 @@ void split_qp(int qp, int log2n, QuantParams* q, int* per, int* rem) {
     q->off = (uint32_t)((1ull << q->shift) / 3);   // intra rounding (quant.py:66-69)
 }
 
+// ===========================================================================
+// CLOSED loop at N = 4, 16, 32: blocks in raster order,
+// every neighbour from the reconstruction built so far.  The schedule is
+// k_intra_rdo8_closed_tag's (nh_intraloop.hip, §4.3a): a worker per block row,
+// rows claimed by an atomic ticket in closed_ticket's order 1, so a worker only
+// waits on a row claimed before its own; block bx of row r needs blocks
+// <= bx + 1 of row r - 1.  A block's bottom row is published as N / 2 tagged
+// 64-bit words ((row + 1) << 32 | int16 pair), one system-scope relaxed store
+// each; the row below polls the N words of its top and top-right blocks until
+// their tags name the row above.  Words past the last full block are never
+// written and read as 0 without a wait.  Row r + 1 overwrites block bx's words
+// only after it has read them for its blocks bx - 1 and bx; the top-left sample
+// is carried from the previous block's top read, and the previous block's
+// right column (LDS) is the left reference.  A wait longer than
+// kClosedNSpinLimit polls, or one that finds the status word set, sets status 1
+// at work[1] and the worker leaves; every other waiter then leaves too.
+// ===========================================================================
+struct ClosedNSet {
+    int64_t base, plane_stride, group_stride;
+    int32_t w, h, pitch, ppg;
+    int32_t bw, bh, row0, plane0;   // full blocks per row / column; first global row / plane of this set
+    int64_t mode0;                  // first mode-map entry of this set
+    int64_t line0;                  // first line word of this set
+    int32_t lw;                     // line words per plane
+    int32_t np;                     // planes in this set
+    int32_t vec_out;                // every row start of lvl / recon is 16-B aligned
+};
+struct ClosedNArgs {
+    const int16_t* src;
+    int32_t* lvl;
+    int16_t* rec;
+    uint8_t* modes;
+    unsigned long long* sse;        // per plane (accumulated)
+    int32_t* work;                  // [0] ticket, [1] status, from word kClosedNLines0 the 64-bit line words
+    ClosedNSet set[NH_MAX_PLANE_SETS];
+    int32_t nsets, total_rows;
+    int32_t order, max_bh;          // closed_ticket: order 1 (row-major across planes), largest bh
+    int64_t lines_total;
+    QuantParams qp;
+    int32_t dq_scale, dq_per;
+};
+constexpr int kClosedNLines0 = 2;           // int32 words before the line words (8-B aligned)
+constexpr int kClosedNSpinLimit = 1 << 20;  // as kSpinLimit of the N = 8 kernel: ~1 s of polling
+
+// the coherent accesses of nh_intraloop.hip's closed loop, restated
+__device__ __forceinline__ int cn_ld_sys(const int32_t* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+__device__ __forceinline__ uint64_t cn_ld_sys64(const uint64_t* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+__device__ __forceinline__ void cn_st_sys64(uint64_t* p, uint64_t v) {
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// The calling wave (all 64 lanes) waits for the N line words x0/2 .. x0/2 + N - 1 of the row
+// above block row `by`: lane k < N polls word k until its tag is `by`; val: the word's int16
+// pair (0 for a word past the last full block, which is not waited for).  False: the wait ran
+// out or another worker has set the status word -- status 1 is set and the caller leaves.
+template <int N>
+__device__ __forceinline__ bool poll_top(const uint64_t* line, int x0, int full_words, int by, int lane, int32_t* work,
+                                         uint32_t& val) {
+    const int wi = x0 / 2 + lane;
+    const bool need = lane < N && wi < full_words;
+    val = 0;
+    int spins = 0;
+    for (;;) {
+        bool ok = true;
+        if (need) {
+            const uint64_t v = cn_ld_sys64(line + wi);
+            ok = (int)(v >> 32) == by;
+            val = (uint32_t)v;
+        }
+        if (__builtin_amdgcn_read_exec() == __ballot(ok)) return true;   // every needed word is there
+        __builtin_amdgcn_s_sleep(1);
+        ++spins;
+        if (spins > kClosedNSpinLimit || ((spins & 1023) == 0 && cn_ld_sys(&work[1]))) {
+            if (lane == 0) atomicMax(&work[1], 1);
+            return false;
+        }
+    }
+}
+
+struct ClosedNRow {
+    const int16_t* src;
+    int32_t* lvl;
+    int16_t* rec;
+    uint64_t* line;
+    uint8_t* modes;     // the row's first mode-map entry
+};
+__device__ __forceinline__ ClosedNRow closed_row(const ClosedNArgs& a, const ClosedNSet& S, int pl, int by) {
+    const int g = pl / S.ppg, c = pl - g * S.ppg;
+    const int64_t off = S.base + (int64_t)g * S.group_stride + (int64_t)c * S.plane_stride;
+    ClosedNRow r;
+    r.src = a.src + off;
+    r.lvl = a.lvl + off;
+    r.rec = a.rec + off;
+    r.line = reinterpret_cast<uint64_t*>(a.work + kClosedNLines0) + S.line0 + (int64_t)pl * S.lw;
+    r.modes = a.modes + S.mode0 + ((int64_t)pl * S.bh + by) * S.bw;
+    return r;
+}
+
+// The neighbours of block (bx, by) into B: thread k of `first` .. first + 3N.  topw: the N line
+// words of the row above (int16 pairs), leftcol: the previous block's right column, tl: the
+// carried top-left sample.
+template <int N>
+__device__ __forceinline__ void closed_stage_refs(RdoNBlock<N>& B, int k, const uint32_t* topw, const int16_t* leftcol,
+                                                  int x0, int y0, int w, int16_t tl) {
+    if (k < 0) return;
+    if (k < 2 * N) {
+        int16_t v = 128;
+        if (y0 > 0 && x0 + k < w) v = (int16_t)(topw[k >> 1] >> ((k & 1) * 16));
+        B.topA[1 + k] = v;
+    } else if (k < 3 * N) {
+        B.leftA[1 + k - 2 * N] = x0 == 0 ? (int16_t)128 : leftcol[k - 2 * N];
+    } else if (k == 3 * N) {
+        const int16_t c = (y0 == 0 || x0 == 0) ? (int16_t)128 : tl;
+        B.topA[0] = c;
+        B.leftA[0] = c;
+        B.ntA = 1 + (y0 == 0 ? 2 * N : min(2 * N, w - x0));   // numpy's slice ends at the plane's right edge
+        B.nlA = 1 + N;                                        // the bottom-left is not coded yet
+        B.best = ULLONG_MAX;
+    }
+}
+
+// N = 4: one wave per block row, a lane per mode, the block in registers (lane_chain4).
+template <bool DST>
+__global__ void __launch_bounds__(64) k_intra_rdo_closed_lane(ClosedNArgs a) {
+    constexpr int N = 4;
+    __shared__ RdoNBlock<N> B;
+    __shared__ uint32_t topw[N];
+    __shared__ int16_t leftcol[N];
+    __shared__ int row_s, stall_s;
+    const int lane = threadIdx.x;
+    const ChainQ cq = make_chainq(a.qp, a.dq_scale, a.dq_per);
+    for (;;) {
+        if (lane == 0) {
+            row_s = atomicAdd(&a.work[0], 1);
+            stall_s = 0;
+        }
+        __syncthreads();
+        const int row = row_s;
+        if (row >= a.total_rows) break;
+        int si, pl, by;
+        closed_ticket(a, row, si, pl, by);
+        const ClosedNSet& S = a.set[si];
+        const ClosedNRow R = closed_row(a, S, pl, by);
+        const int y0 = by * N, full_words = S.bw * (N / 2);
+        int16_t tl_next = 128;
+        unsigned long long row_sse = 0;
+        for (int bx = 0; bx < S.bw; ++bx) {
+            const int x0 = bx * N;
+            int16_t ov = 0;
+            if (lane < N * N) ov = R.src[(int64_t)(y0 + lane / N) * S.pitch + x0 + (lane % N)];
+            if (by > 0) {
+                uint32_t val;
+                if (!poll_top<N>(R.line, x0, full_words, by, lane, a.work, val)) stall_s = 1;
+                if (lane < N) topw[lane] = val;
+            }
+            __syncthreads();
+            if (stall_s) break;
+            if (lane < N * N) B.orig[lane] = ov;
+            closed_stage_refs<N>(B, lane - N * N, topw, leftcol, x0, y0, S.w, tl_next);
+            __syncthreads();
+            if (lane == 0) B.dc = block_dc<N>(B);
+            tl_next = B.topA[N];
+            __syncthreads();
+            int32_t Lv[N][N];
+            uint32_t Rp[N][N / 2];
+            unsigned long long key = ULLONG_MAX;
+            if (lane < kModesN) key = (lane_chain4<DST>(B, lane, cq, Lv, Rp) << 6) | (unsigned long long)lane;
+            unsigned long long best = key;
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) {
+                const unsigned long long o = __shfl_xor(best, m);
+                best = o < best ? o : best;
+            }
+            if (key == best) {   // one lane: the mode is part of the key
+                // publish the bottom row first (the next row polls these words)
+                const uint64_t tag = (uint64_t)(uint32_t)(by + 1) << 32;
+#pragma unroll
+                for (int q = 0; q < N / 2; ++q) cn_st_sys64(R.line + x0 / 2 + q, tag | Rp[N - 1][q]);
+#pragma unroll
+                for (int i = 0; i < N; ++i) {
+                    leftcol[i] = (int16_t)(Rp[i][N / 2 - 1] >> 16);
+                    const int64_t o = (int64_t)(y0 + i) * S.pitch + x0;
+                    store_lvl_row<N>(R.lvl + o, Lv[i], S.vec_out);
+                    store_rec_row<N>(R.rec + o, Rp[i], S.vec_out);
+                }
+                R.modes[bx] = (uint8_t)lane;
+                row_sse += best >> 6;
+            }
+            __syncthreads();   // leftcol is there; B is free for the next block
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) row_sse += __shfl_xor(row_sse, m);
+        if (lane == 0 && row_sse) atomicAdd(&a.sse[S.plane0 + pl], row_sse);
+        const int stalled = stall_s;
+        __syncthreads();       // before lane 0 resets stall_s for the next row
+        if (stalled) break;
+    }
+}
+
+// N = 16 / 32: one 224-lane workgroup per block row, N lanes per (block, mode) chain
+// (tile_chain): 14 chains over 3 rounds at N = 16, 7 chains over 5 rounds at N = 32, then chain 0
+// runs the winner once more and stores its levels and recon.  Wave 0 polls; the words and the
+// stall flag reach the others through LDS and a workgroup barrier.  Every thread passes the same
+// barriers: the stall exit is taken by all of them after the same barrier.
+template <int N>
+__global__ void __launch_bounds__(224) k_intra_rdo_closed_tile(ClosedNArgs a) {
+    constexpr int NT = 224, NC = NT / N, ROUNDS = (kModesN + NC - 1) / NC, P = N + 1;
+    constexpr int OV = (N * N + NT - 1) / NT;   // source samples per thread
+    static_assert(3 * N + 1 <= NT && N <= 64, "neighbour staging and the poll need that many threads");
+    __shared__ RdoNBlock<N> B;
+    __shared__ int32_t tile[NC][N][P];
+    __shared__ int16_t refs[NC][3 * N + 2];
+    __shared__ uint32_t topw[N];
+    __shared__ int16_t leftcol[N];
+    __shared__ int row_s, stall_s;
+    const int tid = threadIdx.x;
+    const int ci = tid / N, t = tid % N;
+    const ChainQ cq = make_chainq(a.qp, a.dq_scale, a.dq_per);
+    for (;;) {
+        if (tid == 0) {
+            row_s = atomicAdd(&a.work[0], 1);
+            stall_s = 0;
+        }
+        __syncthreads();
+        const int row = row_s;
+        if (row >= a.total_rows) break;
+        int si, pl, by;
+        closed_ticket(a, row, si, pl, by);
+        const ClosedNSet& S = a.set[si];
+        const ClosedNRow R = closed_row(a, S, pl, by);
+        const int y0 = by * N, full_words = S.bw * (N / 2);
+        int16_t tl_next = 128;              // thread 3N's
+        unsigned long long row_sse = 0;     // thread 0's
+        for (int bx = 0; bx < S.bw; ++bx) {
+            const int x0 = bx * N;
+            int16_t ov[OV];
+#pragma unroll
+            for (int k = 0; k < OV; ++k) {
+                const int e = tid + k * NT;
+                ov[k] = e < N * N ? R.src[(int64_t)(y0 + e / N) * S.pitch + x0 + (e % N)] : (int16_t)0;
+            }
+            if (by > 0 && tid < 64) {       // wave 0
+                uint32_t val;
+                if (!poll_top<N>(R.line, x0, full_words, by, tid, a.work, val)) stall_s = 1;
+                if (tid < N) topw[tid] = val;
+            }
+            __syncthreads();
+            if (stall_s) break;             // the same value in every thread: written before the barrier only
+#pragma unroll
+            for (int k = 0; k < OV; ++k) {
+                const int e = tid + k * NT;
+                if (e < N * N) B.orig[e] = ov[k];
+            }
+            closed_stage_refs<N>(B, tid, topw, leftcol, x0, y0, S.w, tl_next);
+            __syncthreads();
+            if (tid == 0) B.dc = block_dc<N>(B);
+            if (tid == 3 * N) tl_next = B.topA[N];
+            __syncthreads();
+            for (int r = 0; r < ROUNDS; ++r) {
+                const int mode = r * NC + ci;
+                if (mode < kModesN) {
+                    uint32_t rcp[N / 2];
+                    unsigned long long sse = tile_chain<N>(B, mode, t, tile[ci], refs[ci], cq, nullptr, false, rcp);
+                    // the chain's SSE: sum over its N lanes (an aligned group of N lanes of the wave)
+#pragma unroll
+                    for (int m = N / 2; m >= 1; m >>= 1) sse += __shfl_xor(sse, m);
+                    if (t == 0) atomicMin(&B.best, (sse << 6) | (unsigned long long)mode);
+                    chain_sync();           // refs / tile are rewritten by the next round
+                }
+            }
+            __syncthreads();                // every chain's key is in B.best
+            if (ci == 0) {
+                const unsigned long long best = B.best;
+                const int mode = (int)(best & 63);
+                const int64_t o = (int64_t)(y0 + t) * S.pitch + x0;
+                uint32_t rcp[N / 2];
+                tile_chain<N>(B, mode, t, tile[0], refs[0], cq, R.lvl + o, S.vec_out != 0, rcp);
+                if (t == N - 1) {           // publish the bottom row first (the next row polls these words)
+                    const uint64_t tag = (uint64_t)(uint32_t)(by + 1) << 32;
+#pragma unroll
+                    for (int q = 0; q < N / 2; ++q) cn_st_sys64(R.line + x0 / 2 + q, tag | rcp[q]);
+                }
+                leftcol[t] = (int16_t)(rcp[N / 2 - 1] >> 16);
+                store_rec_row<N>(R.rec + o, rcp, S.vec_out != 0);
+                if (t == 0) {
+                    R.modes[bx] = (uint8_t)mode;
+                    row_sse += best >> 6;
+                }
+            }
+            __syncthreads();                // leftcol is there; B, topw are free for the next block
+        }
+        if (tid == 0 && row_sse) atomicAdd(&a.sse[S.plane0 + pl], row_sse);
+        const int stalled = stall_s;
+        __syncthreads();                    // before thread 0 resets stall_s for the next row
+        if (stalled) break;
+    }
+}
+
+// Samples outside full NxN blocks read as 0 (Plane.zeros) by the closed loop.
+__global__ void __launch_bounds__(256) k_zero_partial_n(int16_t* rec, ClosedNSet S, int n) {
+    const int p = blockIdx.y;
+    const int g = p / S.ppg, c = p - g * S.ppg;
+    int16_t* r = rec + S.base + (int64_t)g * S.group_stride + (int64_t)c * S.plane_stride;
+    const int fw = S.bw * n, fh = S.bh * n;
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < (int64_t)S.w * S.h; i += (int64_t)gridDim.x * 256) {
+        const int y = (int)(i / S.w), x = (int)(i - (int64_t)y * S.w);
+        if (x >= fw || y >= fh) r[(int64_t)y * S.pitch + x] = 0;
+    }
+}
+
+// The argument checks shared by the open- and the closed-loop entry points; `who` names the caller.
+int check_rdo_n_args(const char* who, const nh_plane_set* sets, int nsets, int block_size, int use_dst, int qp) {
+    const std::string w(who);
+    if (block_size != 4 && block_size != 8 && block_size != 16 && block_size != 32) {
+        set_error(w + ": block_size must be 4, 8, 16 or 32");
+        return NH_EARG;
+    }
+    if (use_dst && block_size != 4) {
+        set_error(w + ": use_dst needs block_size 4 (transform.py:138-141)");
+        return NH_EARG;
+    }
+    if (qp < 0 || qp > 51) {
+        set_error(w + ": qp outside 0..51");
+        return NH_EARG;
+    }
+    if (nsets < 1 || nsets > NH_MAX_PLANE_SETS) {
+        set_error(w + ": nsets outside 1..8");
+        return NH_EARG;
+    }
+    for (int k = 0; k < nsets; ++k) {
+        const nh_plane_set& S = sets[k];
+        const int64_t planes = (int64_t)S.planes_per_group * S.num_groups;
+        if (S.width < 0 || S.height < 0 || S.pitch < S.width || S.planes_per_group < 1 || S.num_groups < 0 ||
+            planes > 65535 || S.base < 0 || S.plane_stride < 0 || S.group_stride < 0) {
+            set_error(w + ": bad plane set");
+            return NH_EARG;
+        }
+    }
+    return NH_OK;
+}
+
+// Rows, planes, mode-map and line-word offsets of the closed loop at block size n.  The sets have
+// passed check_rdo_n_args' plane-set test.  NH_EARG: a plane wider or higher than 65535 samples,
+// or 2^30 block rows and more.
+int closed_n_layout(const nh_plane_set* sets, int nsets, int n, ClosedNArgs& a) {
+    int64_t rows = 0, planes = 0, modes = 0, lines = 0;
+    a.max_bh = 0;
+    for (int k = 0; k < nsets; ++k) {
+        const nh_plane_set& p = sets[k];
+        if (p.width > 65535 || p.height > 65535) return NH_EARG;
+        ClosedNSet& S = a.set[k];
+        S.base = p.base;
+        S.plane_stride = p.plane_stride;
+        S.group_stride = p.group_stride;
+        S.w = p.width;
+        S.h = p.height;
+        S.pitch = p.pitch;
+        S.ppg = p.planes_per_group;
+        S.bw = p.width / n;
+        S.bh = S.bw ? p.height / n : 0;   // a plane narrower than a block has no row to code
+        S.row0 = (int32_t)rows;
+        S.plane0 = (int32_t)planes;
+        S.mode0 = modes;
+        S.lw = (p.width + 1) / 2 + n;     // int16 pairs + the top-right read past the last block
+        S.line0 = lines;
+        const int64_t np = (int64_t)p.planes_per_group * p.num_groups;
+        S.np = (int32_t)np;
+        S.vec_out = !(p.pitch & 7) && !((p.base | p.plane_stride | p.group_stride) & 7);
+        if (S.bh > a.max_bh) a.max_bh = S.bh;
+        rows += np * S.bh;
+        planes += np;
+        modes += np * (p.width / n) * (p.height / n);
+        lines += np * S.lw;
+        if (rows >= (1ll << 30)) return NH_EARG;
+    }
+    a.nsets = nsets;
+    a.total_rows = (int32_t)rows;
+    a.order = 1;
+    a.lines_total = lines;
+    return NH_OK;
+}
+
+template <class K>
+int launch_closed_n(K kern, int threads, const ClosedNArgs& a, hipStream_t s) {
+    // persistent workers: one per row, capped at what can be resident (a worker only ever waits on
+    // a row claimed before its own, so fewer workers than rows is always safe)
+    int cus = 0, per_cu = 0;
+    NH_TRY(device_cus(&cus));
+    NH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, 0));
+    const int64_t cap = (int64_t)std::max(1, per_cu) * cus;
+    kern<<<(unsigned)(a.total_rows < cap ? a.total_rows : cap), threads, 0, s>>>(a);
+    NH_HIP(hipGetLastError());
+    return NH_OK;
+}
+
 }  // namespace
 }  // namespace nh
 
@@ -483,31 +914,7 @@ extern "C" int nh_intra_rdo_planes_n(const int16_t* d_src, const nh_plane_set* s
         set_error("nh_intra_rdo_planes_n: null argument");
         return NH_EARG;
     }
-    if (block_size != 4 && block_size != 8 && block_size != 16 && block_size != 32) {
-        set_error("nh_intra_rdo_planes_n: block_size must be 4, 8, 16 or 32");
-        return NH_EARG;
-    }
-    if (use_dst && block_size != 4) {
-        set_error("nh_intra_rdo_planes_n: use_dst needs block_size 4 (transform.py:138-141)");
-        return NH_EARG;
-    }
-    if (qp < 0 || qp > 51) {
-        set_error("nh_intra_rdo_planes_n: qp outside 0..51");
-        return NH_EARG;
-    }
-    if (nsets < 1 || nsets > NH_MAX_PLANE_SETS) {
-        set_error("nh_intra_rdo_planes_n: nsets outside 1..8");
-        return NH_EARG;
-    }
-    for (int k = 0; k < nsets; ++k) {
-        const nh_plane_set& S = sets[k];
-        const int64_t planes = (int64_t)S.planes_per_group * S.num_groups;
-        if (S.width < 0 || S.height < 0 || S.pitch < S.width || S.planes_per_group < 1 || S.num_groups < 0 ||
-            planes > 65535 || S.base < 0 || S.plane_stride < 0 || S.group_stride < 0) {
-            set_error("nh_intra_rdo_planes_n: bad plane set");
-            return NH_EARG;
-        }
-    }
+    NH_TRY(check_rdo_n_args("nh_intra_rdo_planes_n", sets, nsets, block_size, use_dst, qp));
     if (block_size == 8) return nh_intra_rdo_planes(d_src, sets, nsets, qp, d_modes, d_lvl, d_recon, d_sse, stream);
 
     const int N = block_size, log2n = N == 4 ? 2 : N == 16 ? 4 : 5;
@@ -550,6 +957,67 @@ extern "C" int nh_intra_rdo_planes_n(const int16_t* d_src, const nh_plane_set* s
         }
         moff += planes * nblk;
         soff += planes;
+    }
+    return NH_OK;
+}
+
+extern "C" int64_t nh_intra_rdo_closed_n_workspace_bytes(const nh_plane_set* sets, int nsets, int block_size) {
+    if (!sets) return -1;
+    if (check_rdo_n_args("nh_intra_rdo_closed_n_workspace_bytes", sets, nsets, block_size, 0, 0)) return -1;
+    if (block_size == 8) return nh_intra_rdo_closed_workspace_bytes(sets, nsets);
+    ClosedNArgs a;
+    if (closed_n_layout(sets, nsets, block_size, a)) return -1;
+    return 4ll * kClosedNLines0 + 8ll * a.lines_total;
+}
+
+extern "C" int nh_intra_rdo_planes_closed_n(const int16_t* d_src, const nh_plane_set* sets, int nsets, int block_size,
+                                            int use_dst, int qp, uint8_t* d_modes, int32_t* d_lvl, int16_t* d_recon,
+                                            int64_t* d_sse, void* d_work, void* stream) {
+    if (!d_src || !sets || !d_modes || !d_lvl || !d_recon || !d_sse || !d_work) {
+        set_error("nh_intra_rdo_planes_closed_n: null argument");
+        return NH_EARG;
+    }
+    NH_TRY(check_rdo_n_args("nh_intra_rdo_planes_closed_n", sets, nsets, block_size, use_dst, qp));
+    if (block_size == 8)
+        return nh_intra_rdo_planes_closed(d_src, sets, nsets, qp, d_modes, d_lvl, d_recon, d_sse, d_work, stream);
+    const int N = block_size, log2n = N == 4 ? 2 : N == 16 ? 4 : 5;
+    ClosedNArgs a{};
+    if (closed_n_layout(sets, nsets, N, a)) {
+        set_error("nh_intra_rdo_planes_closed_n: bad plane set (sizes <= 65535, < 2^30 block rows)");
+        return NH_EARG;
+    }
+    if ((uintptr_t)d_work & 7) {
+        set_error("nh_intra_rdo_planes_closed_n: workspace must be 8-byte aligned");
+        return NH_EARG;
+    }
+    int per, rem;
+    split_qp(qp, log2n, &a.qp, &per, &rem);
+    a.dq_scale = dequant_scale(rem);
+    a.dq_per = per;
+    a.src = d_src;
+    a.lvl = d_lvl;
+    a.rec = d_recon;
+    a.modes = d_modes;
+    a.sse = (unsigned long long*)d_sse;
+    a.work = (int32_t*)d_work;
+    const bool aligned = !((uintptr_t)d_lvl & 15) && !((uintptr_t)d_recon & 15);
+    const hipStream_t s = as_stream(stream);
+    NH_HIP(hipMemsetAsync(d_work, 0, 4ull * kClosedNLines0 + 8ull * a.lines_total, s));
+    for (int k = 0; k < nsets; ++k) {
+        a.set[k].vec_out = a.set[k].vec_out && aligned;
+        if (a.set[k].np > 0 && (int64_t)a.set[k].w * a.set[k].h > 0)
+            k_zero_partial_n<<<dim3(64, (unsigned)a.set[k].np), 256, 0, s>>>(d_recon, a.set[k], N);
+    }
+    NH_HIP(hipGetLastError());
+    if (a.total_rows > 0) {
+        if (N == 4) {
+            if (use_dst) NH_TRY(launch_closed_n(k_intra_rdo_closed_lane<true>, 64, a, s));
+            else NH_TRY(launch_closed_n(k_intra_rdo_closed_lane<false>, 64, a, s));
+        } else if (N == 16) {
+            NH_TRY(launch_closed_n(k_intra_rdo_closed_tile<16>, 224, a, s));
+        } else {
+            NH_TRY(launch_closed_n(k_intra_rdo_closed_tile<32>, 224, a, s));
+        }
     }
     return NH_OK;
 }

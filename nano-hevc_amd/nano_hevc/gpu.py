@@ -401,6 +401,53 @@ def intra_rdo_closed(src, sets: Sequence[PlaneSet], qp: int = 32, lvl=None, rec=
     return modes[:nmodes], lvl, rec, sse[:nplanes]
 
 
+def intra_rdo_closed_n(src, sets: Sequence[PlaneSet], block_size: int, qp: int = 32, use_dst: bool = False,
+                       lvl=None, rec=None, stream=None):
+    """Config 3 in CLOSED loop at block size N = ``block_size`` in {4, 8, 16, 32}
+     over every plane of ``sets``: the best of the 35 intra modes
+    per full NxN block, blocks in raster order, neighbours from the reconstruction,
+    row wavefront on the device.  ``use_dst`` (N = 4 only) selects the 4x4 DST-VII.
+    Returns (modes uint8 [sum of per-plane (h/N)*(w/N), set order], lvl int32
+    (samples outside full blocks keep the caller's contents), recon int16 (0
+    outside full blocks), sse int64 per plane).  A bad block size, QP outside
+    0..51 or ``use_dst`` with N != 4 raises ValueError; a stalled wavefront raises
+    RuntimeError.  N = 8 runs the ``intra_rdo_closed`` kernels."""
+    torch = _torch()
+    _need(src, torch.int16, "intra_rdo_closed_n(src)")
+    n = int(block_size)
+    if n not in (4, 8, 16, 32):
+        raise ValueError(f"intra_rdo_closed_n: block_size must be 4, 8, 16 or 32, got {block_size}")
+    sets_fit(sets, src.numel(), "intra_rdo_closed_n")
+    nmodes = sum((s.width // n) * (s.height // n) * s.planes_per_group * s.num_groups for s in sets)
+    nplanes = sum(s.planes_per_group * s.num_groups for s in sets)
+    dev = src.device
+    if lvl is None:
+        lvl = torch.zeros(src.shape, dtype=torch.int32, device=dev)
+    if rec is None:
+        rec = torch.zeros(src.shape, dtype=torch.int16, device=dev)
+    _need(lvl, torch.int32, "intra_rdo_closed_n(lvl)")
+    _need(rec, torch.int16, "intra_rdo_closed_n(rec)")
+    if lvl.numel() < src.numel() or rec.numel() < src.numel():
+        raise ValueError("intra_rdo_closed_n: lvl / rec smaller than src")
+    L = _lib.load()
+    arr = (PlaneSet * max(1, len(sets)))(*sets)
+    wb = int(L.nh_intra_rdo_closed_n_workspace_bytes(arr, len(sets), n))
+    if wb < 0:
+        raise ValueError("intra_rdo_closed_n: bad argument: " + L.nh_last_error().decode(errors="replace"))
+    modes = torch.zeros(max(1, nmodes), dtype=torch.uint8, device=dev)
+    sse = torch.zeros(max(1, nplanes), dtype=torch.int64, device=dev)
+    work = torch.empty(max(2, (wb + 3) // 4), dtype=torch.int32, device=dev)
+    st = C.c_void_p(_stream(stream, dev))
+    check(L.nh_intra_rdo_planes_closed_n(src.data_ptr(), arr, len(sets), n, int(bool(use_dst)), int(qp),
+                                         modes.data_ptr(), lvl.data_ptr(), rec.data_ptr(), sse.data_ptr(),
+                                         work.data_ptr(), st), "intra_rdo_closed_n")
+    status = C.c_int(0)
+    check(L.nh_intra_rdo_closed_status(work.data_ptr(), C.byref(status), st))
+    if status.value:
+        raise RuntimeError("intra_rdo_closed_n: the wavefront stalled (device status word set)")
+    return modes[:nmodes], lvl, rec, sse[:nplanes]
+
+
 def dequant_inv8x8(lvl, sets: Sequence[PlaneSet], qp: int = 32, out=None, stream=None):
     """Stage R of the decoder, the mirror of ``fwd8x8_quant``:
     inverse_transform(dequantize_block(level, qp)).astype(int16) on every full
