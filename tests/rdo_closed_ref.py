@@ -17,22 +17,22 @@ def wide_picture(h, w, seed):
     return ((picture(h, w, seed).astype(np.int32) - 128) * 32 + 128).astype(np.int16)
 
 
-def _costs(orig, rec, x, y, n, qp, use_dst):
-    """Per mode (levels, recon, sse) of the block at (x, y) with neighbours from ``rec``."""
+def predict(rec, x, y, n, mode):
+    """Mode ``mode`` of the block at (x, y) with neighbours from the reconstruction ``rec``."""
     top, left, tl = neighbors(rec, x, y, n)
+    if mode == 0:
+        return O.intra_planar(top, left, int(top[-1]), int(left[-1]), n)
+    if mode == 1:
+        return O.intra_dc(top, left, n)
     top2, _, _ = neighbors(rec, x, y, 2 * n)      # truncated at the right edge; past the last full block: 0
     topa = np.concatenate([[tl], top2]).astype(np.int16)
     lefta = np.concatenate([[tl], left]).astype(np.int16)      # the N reconstructed samples only
-    out = []
-    for m in range(35):
-        if m == 0:
-            pred = O.intra_planar(top, left, int(top[-1]), int(left[-1]), n)
-        elif m == 1:
-            pred = O.intra_dc(top, left, n)
-        else:
-            pred = O.intra_angular(topa, lefta, tl, m, n)
-        out.append(chain(orig, pred, qp, n, use_dst))
-    return out
+    return O.intra_angular(topa, lefta, tl, mode, n)
+
+
+def _costs(orig, rec, x, y, n, qp, use_dst):
+    """Per mode (levels, recon, sse) of the block at (x, y) with neighbours from ``rec``."""
+    return [chain(orig, predict(rec, x, y, n, m), qp, n, use_dst) for m in range(35)]
 
 
 def _walk(src, n, qp, use_dst, lvl, rec):
