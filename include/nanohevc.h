@@ -406,6 +406,41 @@ int nh_intra_decode_planes_closed(const uint8_t* d_modes, const int32_t* d_lvl,
                                   const nh_plane_set* sets, int nsets, int qp,
                                   int16_t* d_recon, void* d_work, void* stream);
 
+/* ---- The same decoder at every HEVC block size ----
+ * N = block_size in {4, 8, 16, 32}; use_dst selects the 4x4 DST-VII and is
+ * allowed only with block_size 4.  Stage R per full NxN block:
+ *   res = inverse_transform(dequantize_block(level, qp), use_dst).astype(int16)
+ * in ring arithmetic mod 2^32, exact for EVERY level value of the input dtype
+ * (lvl_bytes 2 = int16, 4 = int32); samples outside full blocks are left
+ * untouched; any width, height, pitch and base (vector row accesses when base,
+ * pitch and strides are multiples of 8 elements and both buffers are 16-B
+ * aligned, element accesses otherwise -- same results).
+ * nh_intra_decode_planes_closed_n is the decoder of
+ * nh_intra_rdo_planes_closed_n: d_modes, d_lvl, the plane sets, block_size,
+ * use_dst and qp are that call's (same mode-map layout, plane numbering, level /
+ * recon layouts); d_recon receives its reconstruction (0 outside full blocks,
+ * also for a plane with no full block).  Stage R into d_recon, a mode pre-pass,
+ * then the encoder's row wavefront with one wave per block row: one prediction
+ * per block from the reconstruction built so far, + residual with the int16
+ * wrap, clip.  d_work: nh_intra_decode_closed_n_workspace_bytes() bytes (the
+ * encoder's size), 8-B aligned, zeroed by the call.  Status word read with
+ * nh_intra_rdo_closed_status: 0 ok, 1 a wavefront wait did not complete, 2 a
+ * mode above 34 in d_modes (the wavefront then returns at once and d_recon is
+ * unspecified).  QP is clamped to 0..51 (get_qp_params).  NH_EARG on the host,
+ * before any HIP call (text in nh_last_error): a block size outside {4, 8, 16,
+ * 32}, use_dst with N != 4, nsets outside 1..8, a bad plane set, a null
+ * pointer, a workspace that is not 8-B aligned, lvl_bytes other than 2 / 4; the
+ * workspace-size call returns a negative value for a refused case.  block_size 8
+ * is checked, then forwarded to the N = 8 entry points above. */
+int nh_dequant_inv_planes_n(const void* d_lvl, int lvl_bytes, int16_t* d_res,
+                            const nh_plane_set* sets, int nsets, int block_size,
+                            int use_dst, int qp, void* stream);
+int64_t nh_intra_decode_closed_n_workspace_bytes(const nh_plane_set* sets, int nsets, int block_size);
+int nh_intra_decode_planes_closed_n(const uint8_t* d_modes, const int32_t* d_lvl,
+                                    const nh_plane_set* sets, int nsets, int block_size,
+                                    int use_dst, int qp, int16_t* d_recon,
+                                    void* d_work, void* stream);
+
 /* ---- Config-4 closed-loop DECODER: TU map + pred-mode map +
  * levels -> the reconstruction of nh_tu_pipeline_planes_closed ----
  * One plane set per call; ctb 32 or 16; width and height multiples of 4.  d_tu and

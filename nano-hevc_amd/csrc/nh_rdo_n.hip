@@ -33,6 +33,10 @@
 // file): the same chains, neighbours from the reconstruction, on the row
 // wavefront of the N = 8 closed loop.  Its residual is int16 whatever the
 // prediction, so the operand bounds above hold for it as they are.
+//
+// The closed loop's DECODER at the same sizes (end of
+// the file): stage P, one prediction per block on the same row wavefront, after
+// stage R (nh_decode_n.hip) has put the residuals in place.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <climits>
@@ -40,6 +44,7 @@
 #include "nh_common.hpp"
 #include "nh_internal.hpp"
 #include "nh_closed_ticket.hpp"
+#include "nh_decode_n.hpp"
 
 namespace nh {
 namespace {
@@ -902,6 +907,188 @@ int launch_closed_n(K kern, int threads, const ClosedNArgs& a, hipStream_t s) {
     return NH_OK;
 }
 
+// ===========================================================================
+// Closed-loop DECODER at N = 4, 16, 32: mode map +
+// levels -> the reconstruction of nh_intra_rdo_planes_closed_n.  Stage R
+// (k_dequant_inv_n, nh_decode_n.hip, earlier on the stream) has put every
+// block's residual into rec; this kernel is the dependent part, stage P.  The
+// schedule is the encoder's above: ClosedNArgs / closed_n_layout / closed_row /
+// poll_top / launch_closed_n as they are, rows claimed by ticket in
+// closed_ticket's order 1, tagged 64-bit line words, the bottom row published
+// before the block's recon stores, the top-left sample and the left column
+// carried along the row, the bounded poll, work[1] honoured by every waiter.
+// One wave per block row at every N -- no workgroup barrier anywhere: lane t
+// holds S = max(1, N * N / 64) neighbouring samples of one block row (1 / 4 / 16
+// at N = 4 / 16 / 32; lanes 16 .. 63 idle at N = 4).  Per block: poll the N words
+// of the top and top-right blocks, ONE prediction (the mode is uniform over the
+// block, so planar / DC / angular are scalar branches) from the staged
+// references in LDS, + residual (int16 wrap), clip, publish, store over the
+// residual the samples came from.  The next block's residual and mode are
+// fetched under the current wait.  Neighbours are read from line words, LDS and
+// registers only, never from rec.  Every neighbour is a clipped 8-bit sample or
+// 128, so the int16 arithmetic of intra.py never wraps in the predictors.
+// ===========================================================================
+// Pre-pass, the test of k_dec_check_modes (nh_intraloop.hip): a mode above 34 sets status 2.
+__global__ void __launch_bounds__(256) k_dec_check_modes_n(const uint8_t* __restrict__ modes, int64_t n,
+                                                           int32_t* status) {
+    bool bad = false;
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) bad |= modes[i] >= kModesN;
+    if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicMax(status, 2);
+}
+
+// The staged references of one block, as ang_ctx reads them: [tl] + 2N top samples, [tl] + N left samples.
+struct DecNRefs {
+    const int16_t *topA, *leftA;
+    int32_t ntA, nlA;
+};
+
+template <int N>
+__global__ void __launch_bounds__(64) k_intra_dec_closed_n(ClosedNArgs a) {
+    constexpr int S = N * N >= 64 ? N * N / 64 : 1;   // samples per lane
+    constexpr int LPR = N / S;                        // lanes per block row
+    constexpr int LG = Log2<N>::v;
+    if (cn_ld_sys(&a.work[1])) return;   // bad mode map: no row is claimed, nothing waits
+    __shared__ int16_t topA[2 * N + 2], leftA[N + 2], rf[3 * N + 2];
+    const int lane = threadIdx.x;
+    const bool act = lane < N * LPR;
+    const int i = act ? lane / LPR : 0, j0 = act ? (lane % LPR) * S : 0;   // this lane: row i, columns j0 .. j0 + S - 1
+    for (;;) {
+        int t = 0;
+        if (lane == 0) t = atomicAdd(&a.work[0], 1);
+        const int row = __builtin_amdgcn_readfirstlane(t);
+        if (row >= a.total_rows) break;
+        int si, pl, by;
+        closed_ticket(a, row, si, pl, by);
+        const ClosedNSet& Z = a.set[si];
+        const ClosedNRow R = closed_row(a, Z, pl, by);
+        const int y0 = by * N, full_words = Z.bw * (N / 2);
+        const bool vec = Z.vec_out != 0;
+        int16_t* p = R.rec + (int64_t)(y0 + i) * Z.pitch + j0;   // this lane's samples of block 0 of the row
+        const uint64_t tag = (uint64_t)(uint32_t)(by + 1) << 32;
+        auto load_res = [&](int x0, int32_t (&r)[S]) {
+            if (!act) {
+#pragma unroll
+                for (int k = 0; k < S; ++k) r[k] = 0;
+            } else if (S >= 4 && vec) {
+#pragma unroll
+                for (int k = 0; k < S; k += 4) {
+                    const uint2 q = *reinterpret_cast<const uint2*>(p + x0 + k);   // 8-B aligned: j0 + k is a multiple of 4
+                    r[k] = (int16_t)q.x;
+                    r[k + 1] = (int32_t)q.x >> 16;
+                    r[k + 2] = (int16_t)q.y;
+                    r[k + 3] = (int32_t)q.y >> 16;
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < S; ++k) r[k] = p[x0 + k];
+            }
+        };
+        int tl = 128;            // top[N - 1] of the previous block: the next block's top-left (its line word is overwritten)
+        int32_t res_n[S];
+        int m_n = 0;
+        load_res(0, res_n);      // bw >= 1: a plane narrower than a block has no row
+        m_n = R.modes[0];
+        if (lane < N) leftA[1 + lane] = 128;   // no block to the left
+        bool stall = false;
+        for (int bx = 0; bx < Z.bw; ++bx) {
+            const int x0 = bx * N;
+            int32_t res[S];
+#pragma unroll
+            for (int k = 0; k < S; ++k) res[k] = res_n[k];
+            const int m = __builtin_amdgcn_readfirstlane(m_n);
+            if (bx + 1 < Z.bw) {   // next block's residual and mode, under this block's wait
+                load_res(x0 + N, res_n);
+                m_n = R.modes[bx + 1];
+            }
+            uint32_t val = 0;
+            if (by > 0) {
+                const bool ok = poll_top<N>(R.line, x0, full_words, by, lane, a.work, val);
+                if (__ballot(!ok)) {
+                    stall = true;
+                    break;
+                }
+            }
+            // stage the references (closed_stage_refs' rules): 128 above the plane and right of it
+            if (lane < N) {
+                const int k = 2 * lane;
+                topA[1 + k] = (y0 > 0 && x0 + k < Z.w) ? (int16_t)val : (int16_t)128;
+                topA[2 + k] = (y0 > 0 && x0 + k + 1 < Z.w) ? (int16_t)(val >> 16) : (int16_t)128;
+            }
+            const int tlc = (by == 0 || bx == 0) ? 128 : tl;
+            if (lane == 0) {
+                topA[0] = (int16_t)tlc;
+                leftA[0] = (int16_t)tlc;
+            }
+            chain_sync();
+            tl = topA[N];
+            DecNRefs B;
+            B.topA = topA;
+            B.leftA = leftA;
+            B.ntA = 1 + (by == 0 ? 2 * N : min(2 * N, Z.w - x0));   // numpy's slice ends at the plane's right edge
+            B.nlA = 1 + N;                                          // the bottom-left is not coded yet
+            int32_t v[S];
+            if (m == 0) {          // planar, tr = top[N - 1], bl = left[N - 1] (intra.py:81-113)
+                const int lv = leftA[1 + i], tr = topA[N], bl = leftA[N];
+#pragma unroll
+                for (int k = 0; k < S; ++k) {
+                    const int x = j0 + k;
+                    v[k] = ((N - 1 - x) * lv + (x + 1) * tr + (N - 1 - i) * topA[1 + x] + (i + 1) * bl + N) >> (LG + 1);
+                }
+            } else if (m == 1) {   // DC (intra.py:46-62), floor division
+                int s = lane < N ? topA[1 + lane] + leftA[1 + lane] : 0;
+#pragma unroll
+                for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
+                const int dc = (s + N) >> (LG + 1);
+#pragma unroll
+                for (int k = 0; k < S; ++k) v[k] = dc;
+            } else {               // angular (intra.py:116-207): the reference array once per block, in LDS
+                const AngCtx ac = ang_ctx<N>(B, m);
+                for (int e = lane; e < 3 * N + 2; e += 64) rf[e] = e <= 3 * N ? (int16_t)ref_at(ac, e - N) : (int16_t)0;
+                chain_sync();
+                const bool vert = m >= 18;
+#pragma unroll
+                for (int k = 0; k < S; ++k) {
+                    const int x = j0 + k;
+                    const int base = vert ? x : i, scan = vert ? i : x;
+                    const int proj = (scan + 1) * ac.angle;
+                    const int16_t* rp = rf + N + base + 1 + (proj >> 5);
+                    v[k] = interp(rp[0], rp[1], proj & 31);
+                }
+            }
+            // reconstruct_block (int16 wrap) + clip_to_pixel_range(., 8)
+#pragma unroll
+            for (int k = 0; k < S; ++k) v[k] = clip8(w16(v[k] + res[k]));
+            // publish the bottom row first (the next row polls these words)
+            if constexpr (S == 1) {
+                const int hi = __shfl(v[0], (lane + 1) & 63, 64);
+                if (act && i == N - 1 && !(j0 & 1))
+                    cn_st_sys64(R.line + (x0 + j0) / 2, tag | (uint32_t)v[0] | ((uint32_t)hi << 16));
+            } else {
+                if (i == N - 1) {
+#pragma unroll
+                    for (int k = 0; k < S; k += 2)
+                        cn_st_sys64(R.line + (x0 + j0 + k) / 2, tag | (uint32_t)v[k] | ((uint32_t)v[k + 1] << 16));
+                }
+            }
+            chain_sync();          // every lane has read leftA / topA / rf of this block
+            if (act && j0 + S == N) leftA[1 + i] = (int16_t)v[S - 1];   // the next block's left column
+            if (act) {
+                if (S >= 4 && vec) {
+#pragma unroll
+                    for (int k = 0; k < S; k += 4)
+                        *reinterpret_cast<uint2*>(p + x0 + k) = make_uint2((uint32_t)v[k] | ((uint32_t)v[k + 1] << 16),
+                                                                           (uint32_t)v[k + 2] | ((uint32_t)v[k + 3] << 16));
+                } else {
+#pragma unroll
+                    for (int k = 0; k < S; ++k) p[x0 + k] = (int16_t)v[k];
+                }
+            }
+        }
+        if (stall) break;
+        chain_sync();              // the next row's first writes to leftA come after this row's last reads
+    }
+}
+
 }  // namespace
 }  // namespace nh
 
@@ -1018,6 +1205,68 @@ extern "C" int nh_intra_rdo_planes_closed_n(const int16_t* d_src, const nh_plane
         } else {
             NH_TRY(launch_closed_n(k_intra_rdo_closed_tile<32>, 224, a, s));
         }
+    }
+    return NH_OK;
+}
+
+extern "C" int64_t nh_intra_decode_closed_n_workspace_bytes(const nh_plane_set* sets, int nsets, int block_size) {
+    if (!sets) return -1;
+    if (check_decode_n_args("nh_intra_decode_closed_n_workspace_bytes", sets, nsets, block_size, 0)) return -1;
+    if (block_size == 8) return nh_intra_decode_closed_workspace_bytes(sets, nsets);
+    ClosedNArgs a;
+    if (closed_n_layout(sets, nsets, block_size, a)) return -1;
+    return 4ll * kClosedNLines0 + 8ll * a.lines_total;
+}
+
+extern "C" int nh_intra_decode_planes_closed_n(const uint8_t* d_modes, const int32_t* d_lvl, const nh_plane_set* sets,
+                                               int nsets, int block_size, int use_dst, int qp, int16_t* d_recon,
+                                               void* d_work, void* stream) {
+    if (!d_modes || !d_lvl || !sets || !d_recon || !d_work) {
+        set_error("nh_intra_decode_planes_closed_n: null argument");
+        return NH_EARG;
+    }
+    NH_TRY(check_decode_n_args("nh_intra_decode_planes_closed_n", sets, nsets, block_size, use_dst));
+    if (block_size == 8) return nh_intra_decode_planes_closed(d_modes, d_lvl, sets, nsets, qp, d_recon, d_work, stream);
+    const int N = block_size;
+    ClosedNArgs a{};
+    if (closed_n_layout(sets, nsets, N, a)) {
+        set_error("nh_intra_decode_planes_closed_n: bad plane set (sizes <= 65535, < 2^30 block rows)");
+        return NH_EARG;
+    }
+    if ((uintptr_t)d_work & 7) {
+        set_error("nh_intra_decode_planes_closed_n: workspace must be 8-byte aligned");
+        return NH_EARG;
+    }
+    if (((uintptr_t)d_lvl & 3) || ((uintptr_t)d_recon & 1)) {
+        set_error("nh_intra_decode_planes_closed_n: buffers must be aligned to their element size");
+        return NH_EARG;
+    }
+    a.lvl = const_cast<int32_t*>(d_lvl);     // read only, by stage R (the encoder's argument block)
+    a.rec = d_recon;
+    a.modes = const_cast<uint8_t*>(d_modes);   // read only
+    a.work = (int32_t*)d_work;
+    const bool aligned = !((uintptr_t)d_recon & 15);
+    const hipStream_t s = as_stream(stream);
+    NH_HIP(hipMemsetAsync(d_work, 0, 4ull * kClosedNLines0 + 8ull * a.lines_total, s));
+    for (int k = 0; k < nsets; ++k) {
+        a.set[k].vec_out = a.set[k].vec_out && aligned;
+        if (a.set[k].np > 0 && (int64_t)a.set[k].w * a.set[k].h > 0)
+            k_zero_partial_n<<<dim3(64, (unsigned)a.set[k].np), 256, 0, s>>>(d_recon, a.set[k], N);
+    }
+    NH_HIP(hipGetLastError());
+    // stage R: every block's residual into d_recon (the wavefront reads neighbours only from line words, LDS
+    // and registers, so a block's residual is read from, and its recon written to, the same place)
+    NH_TRY(nh_dequant_inv_planes_n(d_lvl, 4, d_recon, sets, nsets, N, use_dst, qp, stream));
+    const ClosedNSet& last = a.set[nsets - 1];
+    const int64_t modes_total = last.mode0 + (int64_t)last.np * (last.w / N) * (last.h / N);
+    if (modes_total > 0)
+        k_dec_check_modes_n<<<(unsigned)std::min<int64_t>(1024, (modes_total + 255) / 256), 256, 0, s>>>(
+            d_modes, modes_total, (int32_t*)d_work + 1);
+    NH_HIP(hipGetLastError());
+    if (a.total_rows > 0) {
+        if (N == 4) NH_TRY(launch_closed_n(k_intra_dec_closed_n<4>, 64, a, s));
+        else if (N == 16) NH_TRY(launch_closed_n(k_intra_dec_closed_n<16>, 64, a, s));
+        else NH_TRY(launch_closed_n(k_intra_dec_closed_n<32>, 64, a, s));
     }
     return NH_OK;
 }

@@ -97,6 +97,9 @@ SIGNATURES = {
     "nh_dequant_inv8x8_planes": ([P, I32, P, C.POINTER(PlaneSet), I32, I32, VP], I32),
     "nh_intra_decode_closed_workspace_bytes": ([C.POINTER(PlaneSet), I32], I64),
     "nh_intra_decode_planes_closed": ([P, P, C.POINTER(PlaneSet), I32, I32, P, P, VP], I32),
+    "nh_dequant_inv_planes_n": ([P, I32, P, C.POINTER(PlaneSet), I32, I32, I32, I32, VP], I32),
+    "nh_intra_decode_closed_n_workspace_bytes": ([C.POINTER(PlaneSet), I32, I32], I64),
+    "nh_intra_decode_planes_closed_n": ([P, P, C.POINTER(PlaneSet), I32, I32, I32, I32, P, P, VP], I32),
     "nh_tu_closed_pred_map": ([P, P, P, C.POINTER(PlaneSet), I32, P, VP], I32),
     "nh_dequant_inv_tu_planes": ([P, I32, P, P, C.POINTER(PlaneSet), I32, I32, I32, VP], I32),
     "nh_tu_decode_closed_workspace_bytes": ([C.POINTER(PlaneSet), I32], I64),

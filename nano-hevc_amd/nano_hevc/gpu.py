@@ -12,6 +12,8 @@ launch the gfx950 kernels through the C ABI on the tensor's current stream.
   intra_rdo_closed    -- config 3 in closed loop (row wavefront); _yuv420_stream: in batches, several in flight
   dequant_inv8x8      -- decoder stage R: dequantise + inverse 8x8 DCT over plane sets (fwd8x8_quant's mirror)
   intra_decode_closed -- the decoder of intra_rdo_closed: modes + levels -> its reconstruction
+  dequant_inv_n       -- decoder stage R at N = 4 (DST / DCT), 8, 16, 32 over plane sets, exact for every level
+  intra_decode_closed_n -- the decoder of intra_rdo_closed_n: modes + levels -> its reconstruction
   tu_pipeline_plane   -- config 4: mixed 4..32 TU reconstruction chain on a plane
   tu_pipeline_planes_compact / tu_levels_widen -- config 4 with exact int16 levels (+ int32 spill)
   tc32_plane          -- config 5: 32x32 chain, butterfly or matrix-core variants
@@ -508,6 +510,82 @@ def intra_decode_closed(modes, lvl, sets: Sequence[PlaneSet], qp: int = 32, rec=
         raise ValueError("intra_decode_closed: a mode above 34 in the mode map")
     if status.value:
         raise RuntimeError("intra_decode_closed: the wavefront stalled (device status word set)")
+    return rec
+
+
+def dequant_inv_n(lvl, sets: Sequence[PlaneSet], block_size: int, qp: int = 32, use_dst: bool = False, out=None,
+                  stream=None):
+    """Stage R of the decoder at block size N = ``block_size`` in {4, 8, 16, 32}
+    (DESIGN.md §3.9a): inverse_transform(dequantize_block(level, qp), use_dst)
+    .astype(int16) on every full NxN block of the int16 or int32 level planes
+    described by ``sets`` inside ``lvl``; exact for every level value of the dtype.
+    ``use_dst`` (N = 4 only) selects the 4x4 DST-VII.  The residual lands at the
+    same raster positions of ``out`` (int16, same shape); samples outside full
+    blocks are left as they are.  Any pitch >= width and any base.  A refusal of
+    the library (bad block size, ``use_dst`` with N != 4, bad plane sets) raises
+    ValueError with its text."""
+    torch = _torch()
+    if not isinstance(lvl, torch.Tensor) or lvl.dtype not in (torch.int16, torch.int32):
+        raise TypeError("dequant_inv_n(lvl): expected an int16 or int32 CUDA/HIP torch tensor")
+    _need(lvl, lvl.dtype, "dequant_inv_n(lvl)")
+    if out is None:
+        out = torch.zeros(lvl.shape, dtype=torch.int16, device=lvl.device)
+    _need(out, torch.int16, "dequant_inv_n(out)")
+    if out.device != lvl.device:
+        raise ValueError("dequant_inv_n: out and lvl on different devices")
+    sets_fit(sets, min(lvl.numel(), out.numel()), "dequant_inv_n")
+    arr = (PlaneSet * max(1, len(sets)))(*sets)
+    check(_lib.load().nh_dequant_inv_planes_n(lvl.data_ptr(), lvl.element_size(), out.data_ptr(), arr, len(sets),
+                                              int(block_size), int(bool(use_dst)), int(qp),
+                                              C.c_void_p(_stream(stream, lvl.device))), "dequant_inv_n")
+    return out
+
+
+def intra_decode_closed_n(modes, lvl, sets: Sequence[PlaneSet], block_size: int, qp: int = 32, use_dst: bool = False,
+                          rec=None, stream=None):
+    """The decoder of ``intra_rdo_closed_n``: from that call's
+    ``modes`` (uint8, its layout), ``lvl`` (int32, source layout), ``sets``,
+    ``block_size``, ``use_dst`` and ``qp``, rebuild its reconstruction -- stage R,
+    then one prediction per block in closed loop on the row wavefront.  Returns
+    recon int16 (source layout, 0 outside full blocks).  QP is clamped to 0..51.
+    A mode above 34, too few modes for the blocks or a refusal of the library (bad
+    block size, ``use_dst`` with N != 4, bad plane sets) raises ValueError; a
+    stalled wavefront raises RuntimeError.  N = 8 runs ``intra_decode_closed``'s
+    kernels."""
+    torch = _torch()
+    _need(lvl, torch.int32, "intra_decode_closed_n(lvl)")
+    _need(modes, torch.uint8, "intra_decode_closed_n(modes)")
+    if modes.device != lvl.device:
+        raise ValueError("intra_decode_closed_n: modes and lvl on different devices")
+    sets_fit(sets, lvl.numel(), "intra_decode_closed_n")
+    n = int(block_size)
+    L = _lib.load()
+    arr = (PlaneSet * max(1, len(sets)))(*sets)
+    wb = int(L.nh_intra_decode_closed_n_workspace_bytes(arr, len(sets), n))
+    if wb < 0:
+        raise ValueError("intra_decode_closed_n: bad argument: " + L.nh_last_error().decode(errors="replace"))
+    nmodes = sum((s.width // n) * (s.height // n) * s.planes_per_group * s.num_groups for s in sets)
+    if modes.numel() < nmodes:
+        raise ValueError(f"intra_decode_closed_n: {modes.numel()} modes for {nmodes} blocks")
+    if rec is None:
+        rec = torch.zeros(lvl.shape, dtype=torch.int16, device=lvl.device)
+    _need(rec, torch.int16, "intra_decode_closed_n(rec)")
+    if rec.device != lvl.device:
+        raise ValueError("intra_decode_closed_n: rec and lvl on different devices")
+    if rec.numel() < lvl.numel():
+        raise ValueError("intra_decode_closed_n: rec smaller than lvl")
+    if nmodes == 0:   # no full block anywhere: the device still zeroes rec, but reads no mode
+        modes = torch.zeros(1, dtype=torch.uint8, device=lvl.device)
+    work = torch.empty(max(2, (wb + 3) // 4), dtype=torch.int32, device=lvl.device)
+    st = C.c_void_p(_stream(stream, lvl.device))
+    check(L.nh_intra_decode_planes_closed_n(modes.data_ptr(), lvl.data_ptr(), arr, len(sets), n, int(bool(use_dst)),
+                                            int(qp), rec.data_ptr(), work.data_ptr(), st), "intra_decode_closed_n")
+    status = C.c_int(0)
+    check(L.nh_intra_rdo_closed_status(work.data_ptr(), C.byref(status), st))
+    if status.value == 2:
+        raise ValueError("intra_decode_closed_n: a mode above 34 in the mode map")
+    if status.value:
+        raise RuntimeError("intra_decode_closed_n: the wavefront stalled (device status word set)")
     return rec
 
 
