@@ -258,9 +258,14 @@ int nh_intra_rdo_planes_n(const int16_t* d_src, const nh_plane_set* sets, int ns
                           int32_t* d_lvl, int16_t* d_recon, int64_t* d_sse, void* stream);
 
 /* Config 4: mixed 4/8/16/32 TU pipeline on one plane over CTU rows
- * [row0, row1): seeded quadtree per CTB (ctb 32 luma / 16
- * chroma), per TU the __main__.py:165-178 DC-vs-planar choice then the full
- * reconstruction chain (DST for 4x4 luma).  d_tu: (h/4)*(w/4) u8 log2 TU size;
+ * [row0, row1): seeded quadtree per CTB, per TU the
+ * __main__.py:165-178 DC-vs-planar choice then the full reconstruction chain.
+ * ctb: 4, 8, 16 or 32 with either value of is_luma (the configurations use 32
+ * for luma and 16 for chroma; any other ctb: NH_EVALUE); is_luma only selects
+ * the DST for 4x4 TUs (0: the DCT) and is independent of ctb.  The same set
+ * holds for nh_tu_pipeline_planes and nh_tu_pipeline_planes_closed; the compact
+ * levels and the decoder family below take ctb 16 or 32, again with either
+ * is_luma.  Width and height multiples of 4.  d_tu: (h/4)*(w/4) u8 log2 TU size;
  * d_work: nh_tu_workspace_bytes(w, h, ctb) bytes of device scratch (currently
  * 0: TUs are found by per-size grid walks; NULL accepted). */
 int64_t nh_tu_workspace_bytes(int w, int h, int ctb);

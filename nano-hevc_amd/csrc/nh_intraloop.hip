@@ -3393,11 +3393,13 @@ extern "C" int nh_tu_pipeline_planes_closed(const int16_t* d_src, const nh_plane
     static const int rec_ctu = NH_KNOB("NH_CLOSED4_REC_CTU", 1);
     a.rec_ctu = rec_ctu && !(set->pitch & 3) && !((set->base | set->plane_stride | set->group_stride) & 3) &&
                 !((uintptr_t)d_recon & 7);
-    // the pair kernel's LDS-DMA source tile: 16-B pieces of whole rows (width, pitch, offsets multiples of
-    // 8 samples, so no piece straddles a row's end) and 32-bit byte offsets within a group of planes;
+    // the pair kernel's LDS-DMA source tile: 16-B pieces of whole rows (width, pitch, offsets and the CTU
+    // origins multiples of 8 samples, so no piece straddles a row's end: at CTB 4 the piece of a CTU at
+    // x = w - 4 would read 4 samples past its row, past the buffer on the last row of the last plane) and
+    // 32-bit byte offsets within a group of planes;
     // A/B knob NH_CLOSED4_SRCTILE = 0: the chains load their samples from global memory
     static const int srctile = NH_KNOB("NH_CLOSED4_SRCTILE", 1);
-    a.srctile = srctile && !(set->width & 7) && !(set->pitch & 7) &&
+    a.srctile = srctile && !(ctb & 7) && !(set->width & 7) && !(set->pitch & 7) &&
                 !((set->base | set->plane_stride | set->group_stride) & 7) && !((uintptr_t)d_src & 15) &&
                 (3 * set->group_stride + (int64_t)set->height * set->pitch) * 2 < (1ll << 31);
     {   // tu_closed_batch_mma's per-lane bases and initial accumulators

@@ -13,7 +13,7 @@ def valid(tu, ctb):
     (n = 1 << v) holding the unit inside the plane, every unit of that square v."""
     tu = np.asarray(tu)
     h4, w4 = tu.shape
-    top = {16: 4, 32: 5}[ctb]
+    top = {4: 2, 8: 3, 16: 4, 32: 5}[ctb]
     for uy in range(h4):
         for ux in range(w4):
             v = int(tu[uy, ux])
@@ -62,14 +62,18 @@ def _preds(rec, x, y, n):
     return O.intra_dc(top, left, n), O.intra_planar(top, left, top[-1], left[-1], n)
 
 
+def pred_energies(src, rec, x, y, n):
+    """(e_dc, e_planar) of the TU (x, y, n): int16-wrapping residual, int64 energies."""
+    o = src[y:y + n, x:x + n]
+    return tuple(int((O.residual(o, p).astype(np.int64) ** 2).sum()) for p in _preds(rec, x, y, n))
+
+
 def pred_map(src, rec, tu, ctb):
     """1 = DC where e_dc <= e_planar (int16-wrapping residual, int64 energies), else 0;
     written to every unit of the TU."""
     pm = np.zeros_like(np.asarray(tu, np.uint8))
     for x, y, n in tus(tu, ctb):
-        dc, pl = _preds(rec, x, y, n)
-        o = src[y:y + n, x:x + n]
-        e = [int((O.residual(o, p).astype(np.int64) ** 2).sum()) for p in (dc, pl)]
+        e = pred_energies(src, rec, x, y, n)
         pm[y // 4:(y + n) // 4, x // 4:(x + n) // 4] = 1 if e[0] <= e[1] else 0
     return pm
 
