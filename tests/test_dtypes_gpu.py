@@ -6,7 +6,6 @@ REFERENCE returned (value, dtype and Python type) or which exception it raised
 the same value bit for bit (float results included: mse / psnr are computed in
 numpy's pairwise summation order on the device) or raise the same builtin
 exception class."""
-import builtins
 import os
 import sys
 
@@ -17,6 +16,7 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
 from dtype_cases import cases  # noqa: E402
+from block_checks import check_dtype_case  # noqa: E402
 
 CASES = cases()
 
@@ -35,21 +35,4 @@ def test_fixture_covers_every_case(fixture):
 
 @pytest.mark.parametrize("name,fn,args,kw", CASES, ids=[c[0] for c in CASES])
 def test_dtype_case_matches_reference(fixture, name, fn, args, kw):
-    import warnings
-    from nano_hevc import intra, quant, metrics, transform
-    f = next(getattr(m, fn) for m in (intra, quant, metrics, transform) if hasattr(m, fn))
-    if "err_" + name in fixture:
-        base = getattr(builtins, str(fixture["errbase_" + name]))
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")
-            with pytest.raises(base):
-                f(*args, **kw)
-        return
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        r = f(*args, **kw)
-    exp = fixture["out_" + name]
-    assert type(r).__name__ == str(fixture["rtype_" + name])
-    got = np.asarray(r)
-    assert got.dtype == exp.dtype and got.shape == exp.shape
-    assert np.array_equal(got, exp, equal_nan=got.dtype.kind == "f")
+    check_dtype_case(fixture, name, fn, args, kw)

@@ -12,6 +12,8 @@ pytestmark = pytest.mark.gpu
 
 from oracle import oracle as O  # noqa: E402  (checker only)
 from natural import natural_residual  # noqa: E402
+from block_checks import (check_chain_config1, check_intra_golden, check_metrics_golden,  # noqa: E402
+                          check_quant_golden, check_transforms_golden)
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -36,50 +38,16 @@ def torch_dev():
 @pytest.mark.parametrize("key,n,dst", [("n4_dst", 4, True), ("n4_dct", 4, False), ("n8_dct", 8, False),
                                        ("n16_dct", 16, False), ("n32_dct", 32, False)])
 def test_shim_transforms_golden(nh, golden, key, n, dst):
-    g = golden("transform.npz")
-    for x, y in zip(g[key + "_fwd_in"], g[key + "_fwd_out"]):
-        out = nh.forward_transform(x, use_dst=dst)
-        assert out.dtype == np.int32 and np.array_equal(out, y)
-    for x, y in zip(g[key + "_inv_in"], g[key + "_inv_out"]):
-        assert np.array_equal(nh.inverse_transform(x, use_dst=dst), y)
+    check_transforms_golden(nh, golden("transform.npz"), key, n, dst)
 
 
 def test_shim_quant_golden(nh, golden):
-    g = golden("quant.npz")
-    for a, qp in enumerate(g["q_qps"]):
-        qp = int(qp)
-        for b, size in enumerate([4, 8, 16, 32]):
-            for c, intra in enumerate([True, False]):
-                out = nh.quantize(g["q_vec32"], qp, size, intra)
-                assert out.dtype == np.int32 and np.array_equal(out, g["q_out32"][a, b, c]), (qp, size, intra)
-                assert np.array_equal(nh.quantize(g["q_vec16"], qp, size, intra), g["q_out16"][a, b, c])
-        assert np.array_equal(nh.dequantize(g["dq_in"], qp, 4), g["dq_out"][a]), qp
+    check_quant_golden(nh, golden("quant.npz"))
 
 
 @pytest.mark.parametrize("n", [4, 8, 16, 32])
 def test_shim_intra_golden(nh, golden, n):
-    g = golden("intra.npz")
-    for s in range(8):
-        top = g[f"n{n}_top"][s, :g[f"n{n}_ntop"][s]]
-        left = g[f"n{n}_left"][s, :g[f"n{n}_nleft"][s]]
-        corner = int(g[f"n{n}_corner"][s])
-        for m in range(35):
-            st = int(g[f"n{n}_status"][s, m])
-            if m == 0:
-                t = top[:n] if top.size >= n else top
-                l = left[:n] if left.size >= n else left
-                fn = lambda: nh.intra_planar_predict(t, l, int(top[min(n, top.size) - 1]),
-                                                     int(left[min(n, left.size) - 1]), n)
-            elif m == 1:
-                fn = lambda: nh.intra_dc_predict(top, left, n)
-            else:
-                fn = lambda: nh.intra_angular_predict(top, left, corner, m, n)
-            if st == 0:
-                out = fn()
-                assert out.dtype == np.int16 and np.array_equal(out, g[f"n{n}_pred"][s, m]), (n, s, m)
-            else:
-                with pytest.raises({1: OverflowError, 2: IndexError}[st]):
-                    fn()
+    check_intra_golden(nh, golden("intra.npz"), n)
 
 
 def test_shim_quirks_and_elementwise(nh, golden):
@@ -100,18 +68,7 @@ def test_shim_quirks_and_elementwise(nh, golden):
 
 def test_shim_chain_config1(nh, golden):
     """Config 1: the README / test_quant.py:283-322 chain, bit-exact per stage."""
-    g = golden("chain.npz")
-    pred = nh.intra_dc_predict(g["c1_top"], g["c1_left"], 4)
-    res = nh.residual_block(g["c1_orig"], pred)
-    coeff = nh.forward_transform(res, use_dst=True)
-    assert np.array_equal(pred, g["c1_pred"]) and np.array_equal(res, g["c1_res"]) and np.array_equal(coeff, g["c1_coeff"])
-    for qp in (20, 22):
-        lvl = nh.quantize_block(coeff, qp)
-        deq = nh.dequantize_block(lvl, qp)
-        rres = nh.inverse_transform(deq, use_dst=True)
-        rec = nh.clip_to_pixel_range(nh.reconstruct_block(pred, rres.astype(np.int16)))
-        for k, v in (("lvl", lvl), ("deq", deq), ("rres", rres), ("recon", rec)):
-            assert np.array_equal(v, g[f"c1_{k}_qp{qp}"]), (k, qp)
+    check_chain_config1(nh, golden("chain.npz"))
 
 
 def test_shim_reference_known_answers(nh):
@@ -515,25 +472,7 @@ def test_fused8x8_rank_layouts_vs_oracle(nh, torch_dev, world):
 
 def test_metrics_golden(nh, golden):
     """metrics.py:7-48 through the device reductions vs the reference's values."""
-    g = golden("metrics.npz")
-    for i, (a, b) in enumerate(zip(g["m_a8"], g["m_b8"])):
-        assert nh.mse(a, b) == g["m_mse"][i]
-        assert nh.psnr(a, b) == g["m_psnr"][i]
-        assert nh.psnr(a, b, peak=1023) == g["m_psnr1023"][i]
-    assert nh.psnr(g["m_a8"][0], g["m_a8"][0]) == float("inf")
-    for i, (a, b) in enumerate(zip(g["m_a16"], g["m_b16"])):
-        assert nh.mse(a, b) == g["m_mse16"][i]
-        assert nh.sad(a, b) == g["m_sad16"][i]
-        assert nh.residual_energy(a) == g["m_energy16"][i]
-    for i, (a, b) in enumerate(zip(g["m_a32"], g["m_b32"])):
-        assert nh.sad(a, b) == g["m_sad32"][i]
-        assert nh.satd_4x4(a, b) == g["m_satd32"][i]
-    for i, (a, b) in enumerate(zip(g["m_s4a"], g["m_s4b"])):
-        assert nh.satd_4x4(a, b) == g["m_satd"][i]
-    for i, e in enumerate(g["m_e64"]):
-        assert nh.residual_energy(e) == g["m_energy64"][i]
-    with pytest.raises(ValueError):
-        nh.satd_4x4(np.arange(8), np.arange(8))
+    check_metrics_golden(nh, golden("metrics.npz"))
 
 
 def test_sse_i16_device(nh, torch_dev):
