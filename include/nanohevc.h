@@ -485,6 +485,41 @@ int nh_tu_decode_planes_closed(const uint8_t* d_tu, const uint8_t* d_pm, const i
                                const nh_plane_set* set, int ctb, int is_luma, int qp,
                                int16_t* d_recon, void* d_work, void* stream);
 
+/* ---- Config 4 with a CHOSEN or a SUPPLIED quadtree, open loop ----
+ * One plane set per call; ctb 32 or 16; width and height multiples of 4; is_luma
+ * only selects the DST for 4x4 TUs.  Per TU §3.4's chain with neighbours from the
+ * SOURCE plane (128 outside it), distortion D = sum (int16)(orig - recon)^2, rate
+ * R = count_nonzero(level) + 1, cost J = D + lambda * R, all int64.
+ * d_lvl int32 and d_recon int16 use the source layout; d_tu (log2 TU size) and
+ * d_pm (1 = DC, 0 = planar) hold (h/4)*(w/4) bytes per plane, planes numbered
+ * g * planes_per_group + c, in every 4x4 unit of the TU; d_stats holds three int64
+ * per plane in that order (sum J, sum D, sum R over the plane's TUs) and is
+ * OVERWRITTEN by the call.  Nothing outside the plane rectangles is written.
+ * Both entry points return NH_EARG, on the host and before any HIP call, for a ctb
+ * other than 16 / 32, a width or height that is no multiple of 4, a qp outside
+ * 0..51 (refused, not clamped), a lambda outside 0..2^31-1, a null pointer and a
+ * bad plane set (nh_last_error has the text); a set without groups or planes is a
+ * no-op that returns 0.
+ *
+ * nh_tu_rd_planes: the TU-size search.  Every aligned candidate TU of every size
+ * 4 .. ctb inside the plane is coded; bottom-up per CTB a node becomes one TU iff
+ * its J <= the sum of its four best children (the parent wins ties; a node that
+ * overhangs the plane must split).  Writes d_lvl, d_recon, d_tu, d_pm, d_stats. */
+int nh_tu_rd_planes(const int16_t* d_src, const nh_plane_set* set, int ctb, int qp, int is_luma,
+                    int64_t lambda, int32_t* d_lvl, int16_t* d_recon, uint8_t* d_tu, uint8_t* d_pm,
+                    int64_t* d_stats, void* stream);
+/* The map-driven encode: d_tu is an INPUT, any partition of every plane into
+ * aligned squares of 4 .. ctb samples (the rule of nh_tu_decode_planes_closed),
+ * whatever made it.  Writes d_lvl, d_recon, d_pm and d_stats for exactly the TUs of
+ * the map; lambda enters only d_stats.  d_work: caller-owned,
+ * nh_tu_encode_map_workspace_bytes() bytes, 4-B aligned, zeroed by the call.
+ * Status word read with nh_intra_rdo_closed_status: 0 ok, 2 a bad map: the encode
+ * then returns at once and the outputs are unspecified (a bad map is memory-safe). */
+int64_t nh_tu_encode_map_workspace_bytes(void);
+int nh_tu_encode_map_planes(const int16_t* d_src, const uint8_t* d_tu, const nh_plane_set* set, int ctb,
+                            int qp, int is_luma, int64_t lambda, int32_t* d_lvl, int16_t* d_recon,
+                            uint8_t* d_pm, int64_t* d_stats, void* d_work, void* stream);
+
 /* ---- Frame I/O and the frame-level intra driver ----
  * Frame.from_yuv420p / Plane.from_buffer + .astype(np.int16) (frame.py:44-54,
  * :87-110) and Frame.to_yuv420p / PackedFrame.to_yuv420p's .astype(np.uint8)

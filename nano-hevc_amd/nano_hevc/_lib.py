@@ -104,6 +104,9 @@ SIGNATURES = {
     "nh_dequant_inv_tu_planes": ([P, I32, P, P, C.POINTER(PlaneSet), I32, I32, I32, VP], I32),
     "nh_tu_decode_closed_workspace_bytes": ([C.POINTER(PlaneSet), I32], I64),
     "nh_tu_decode_planes_closed": ([P, P, P, C.POINTER(PlaneSet), I32, I32, I32, P, P, VP], I32),
+    "nh_tu_rd_planes": ([P, C.POINTER(PlaneSet), I32, I32, I32, I64, P, P, P, P, P, VP], I32),
+    "nh_tu_encode_map_workspace_bytes": ([], I64),
+    "nh_tu_encode_map_planes": ([P, P, C.POINTER(PlaneSet), I32, I32, I32, I64, P, P, P, P, P, VP], I32),
     "nh_widen_u8_i16": ([P, P, I64, VP], I32),
     "nh_narrow_i16_u8": ([P, P, I64, VP], I32),
     "nh_encode_intra_planes": ([P, I32, C.POINTER(PlaneSet), I32, P, P, P, P, P, VP], I32),

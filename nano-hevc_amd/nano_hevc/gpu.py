@@ -26,6 +26,8 @@ launch the gfx950 kernels through the C ABI on the tensor's current stream.
   dequant_inv_tu      -- decoder stage R over a TU map (4x4 DST / DCT, 8, 16, 32), exact for every level
   tu_decode_closed    -- the decoder of tu_pipeline_closed: TU map + pred-mode map + levels -> its reconstruction
   tu_decode_closed_yuv420 -- the same over a YUV420 stream, luma and chroma wavefronts concurrent
+  tu_rd_planes        -- config 4 with the quadtree chosen by integer RD cost (open loop); tu_rd_plane, tu_rd_yuv420
+  tu_encode_map_planes -- config 4 on a quadtree the caller supplies (open loop)
   widen_u8 / narrow_u8 -- frame I/O casts (YUV420p bytes <-> int16 planes)
   encode_intra_yuv420 -- encode_frame_intra (DC vs planar per block) over a frame stream
   block_server_stop / block_server_set_idle_us / block_server_stats -- the per-block
@@ -1083,6 +1085,112 @@ def tu_decode_closed_yuv420(tu_luma, pm_luma, tu_chroma, pm_chroma, lvl, luma: P
             raise e
         raise
     return rec
+
+
+def _tu_rd_prepare(src, pset: PlaneSet, ctb: int, qp: int, lam: int, lvl, rec, what: str):
+    """Argument checks and default outputs shared by the search and the map-driven
+    encode; returns (lvl, rec, planes)."""
+    torch = _torch()
+    _need(src, torch.int16, f"{what}(src)")
+    _tu_set_check(pset, ctb, what)
+    if not 0 <= int(qp) <= 51:
+        raise ValueError(f"{what}: qp must be in 0..51")
+    if not 0 <= int(lam) <= 2 ** 31 - 1:
+        raise ValueError(f"{what}: lam must be in 0..2^31-1")
+    sets_fit([pset], src.numel(), what)
+    dev = src.device
+    if lvl is None:
+        lvl = torch.zeros(src.shape, dtype=torch.int32, device=dev)
+    if rec is None:
+        rec = torch.zeros(src.shape, dtype=torch.int16, device=dev)
+    _need(lvl, torch.int32, f"{what}(lvl)")
+    _need(rec, torch.int16, f"{what}(rec)")
+    if lvl.device != dev or rec.device != dev:
+        raise ValueError(f"{what}: lvl / rec and src on different devices")
+    sets_fit([pset], min(lvl.numel(), rec.numel()), f"{what}(lvl, rec)")
+    return lvl, rec, pset.planes_per_group * pset.num_groups
+
+
+def tu_rd_planes(src, pset: PlaneSet, ctb: int, qp: int = 32, lam: int = 0, is_luma: bool = True, lvl=None, rec=None,
+                 tu=None, pm=None, stream=None):
+    """Config 4 with the quadtree CHOSEN by integer RD cost, open loop (DESIGN.md
+    §3.4a), over every plane of one plane set: every aligned candidate TU of every
+    size 4..ctb runs §3.4's chain (neighbours from the source, 128 outside the
+    plane), J = D + lam * R with D = sum (int16)(orig - rec)^2 and R =
+    count_nonzero(level) + 1; bottom-up per CTB a node becomes one TU iff its J <=
+    the sum of its four best children (the parent wins ties, a node that overhangs
+    the plane splits).  ``ctb`` 16 or 32, ``qp`` 0..51, ``lam`` 0..2^31-1.
+    Returns (lvl int32, rec int16 -- source layout --, tu uint8 log2 TU size, pm
+    uint8 1 = DC / 0 = planar -- (planes, h/4, w/4) --, stats int64 (planes, 3):
+    sum J, sum D, sum R over the plane's TUs)."""
+    torch = _torch()
+    lvl, rec, planes = _tu_rd_prepare(src, pset, ctb, qp, lam, lvl, rec, "tu_rd_planes")
+    dev = src.device
+    shape = (planes, pset.height // 4, pset.width // 4)
+    if tu is None:
+        tu = torch.zeros(shape, dtype=torch.uint8, device=dev)
+    if pm is None:
+        pm = torch.zeros(shape, dtype=torch.uint8, device=dev)
+    _tu_map_need(tu, pset, dev, "tu_rd_planes(tu)")
+    _tu_map_need(pm, pset, dev, "tu_rd_planes(pm)")
+    stats = torch.empty((planes, 3), dtype=torch.int64, device=dev)
+    check(_lib.load().nh_tu_rd_planes(src.data_ptr(), C.byref(pset), int(ctb), int(qp), int(bool(is_luma)), int(lam),
+                                      lvl.data_ptr(), rec.data_ptr(), tu.data_ptr(), pm.data_ptr(), stats.data_ptr(),
+                                      C.c_void_p(_stream(stream, dev))), "tu_rd_planes")
+    return lvl, rec, tu, pm, stats
+
+
+def tu_rd_plane(src2d, ctb: int, qp: int = 32, lam: int = 0, is_luma: bool = True, stream=None):
+    """``tu_rd_planes`` on one int16 plane (H, W).  Returns (lvl (H, W), rec (H, W),
+    tu (H/4, W/4), pm (H/4, W/4), stats (3,))."""
+    torch = _torch()
+    _need(src2d, torch.int16, "tu_rd_plane")
+    if src2d.dim() != 2:
+        raise ValueError("tu_rd_plane: expected a 2-D plane")
+    h, w = src2d.shape
+    lvl, rec, tu, pm, stats = tu_rd_planes(src2d, plane_set(0, w, h, w), ctb, qp, lam, is_luma, stream=stream)
+    return lvl, rec, tu[0], pm[0], stats[0]
+
+
+def tu_encode_map_planes(src, tu, pset: PlaneSet, ctb: int, qp: int = 32, lam: int = 0, is_luma: bool = True,
+                         lvl=None, rec=None, pm=None, stream=None):
+    """Config 4 on a quadtree the CALLER supplies, open loop: every
+    TU of the map ``tu`` (uint8 log2 TU size per 4x4 unit, (planes, h/4, w/4)) runs
+    §3.4's chain once at its size.  Map-driven: any ``tu`` that partitions every plane
+    into aligned squares of 4..ctb samples is coded, whatever made it; any other map
+    raises ValueError (the outputs are then unspecified).  ``lam`` enters only
+    ``stats``.  Returns (lvl, rec, pm, stats) as ``tu_rd_planes``."""
+    torch = _torch()
+    lvl, rec, planes = _tu_rd_prepare(src, pset, ctb, qp, lam, lvl, rec, "tu_encode_map_planes")
+    dev = src.device
+    _tu_map_need(tu, pset, dev, "tu_encode_map_planes(tu)")
+    if pm is None:
+        pm = torch.zeros((planes, pset.height // 4, pset.width // 4), dtype=torch.uint8, device=dev)
+    _tu_map_need(pm, pset, dev, "tu_encode_map_planes(pm)")
+    stats = torch.empty((planes, 3), dtype=torch.int64, device=dev)
+    L = _lib.load()
+    work = torch.empty((int(L.nh_tu_encode_map_workspace_bytes()) + 7) // 8, dtype=torch.int64, device=dev)
+    st = _stream(stream, dev)
+    check(L.nh_tu_encode_map_planes(src.data_ptr(), tu.data_ptr(), C.byref(pset), int(ctb), int(qp), int(bool(is_luma)),
+                                    int(lam), lvl.data_ptr(), rec.data_ptr(), pm.data_ptr(), stats.data_ptr(),
+                                    work.data_ptr(), C.c_void_p(st)), "tu_encode_map_planes")
+    if planes:
+        status = C.c_int(0)
+        check(L.nh_intra_rdo_closed_status(work.data_ptr(), C.byref(status), C.c_void_p(st)))
+        if status.value:
+            raise ValueError("tu_encode_map_planes: bad map (tu is no partition into aligned squares of 4..ctb "
+                             "samples inside the plane; status %d)" % status.value)
+    return lvl, rec, pm, stats
+
+
+def tu_rd_yuv420(src, luma: PlaneSet, chroma: PlaneSet, qp: int = 32, lam: int = 0, lvl=None, rec=None, stream=None):
+    """``tu_rd_planes`` over a YUV420 stream: the luma set with CTB 32 and the DST, the
+    U+V set with CTB 16 and without it (the pairing of ``tu_pipeline_closed_yuv420``),
+    in sequence on one stream into shared ``lvl`` / ``rec``.
+    Returns (lvl, rec, (tu, pm, stats) of luma, (tu, pm, stats) of chroma)."""
+    lvl, rec, tu_y, pm_y, st_y = tu_rd_planes(src, luma, 32, qp, lam, True, lvl, rec, stream=stream)
+    lvl, rec, tu_c, pm_c, st_c = tu_rd_planes(src, chroma, 16, qp, lam, False, lvl, rec, stream=stream)
+    return lvl, rec, (tu_y, pm_y, st_y), (tu_c, pm_c, st_c)
 
 
 _PIPE_STREAMS = {}
