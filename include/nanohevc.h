@@ -385,6 +385,42 @@ int nh_intra_rdo_planes_closed_n(const int16_t* d_src, const nh_plane_set* sets,
                                  int32_t* d_lvl, int16_t* d_recon, int64_t* d_sse,
                                  void* d_work, void* stream);
 
+/* Config 3 with a RATE term, at every HEVC block size (DESIGN.md §3.3b open
+ * loop, §3.7b closed loop): the 35 chains of nh_intra_rdo_planes_n /
+ * nh_intra_rdo_planes_closed_n per full NxN block, unchanged, and per mode
+ *   D = sum (int16)(orig - recon)^2, R = count_nonzero(level) + 1,
+ *   J = D + lambda * R   (int64; §3.4a's rate, so configs 3 and 4 compare).
+ * The lowest J wins, ties go to the lowest mode; in the closed loop the later
+ * blocks' neighbours are the J winner's reconstruction, and (d_modes, d_lvl)
+ * decode with nh_intra_decode_planes_closed_n as they are.  lambda = 0 gives the
+ * modes, levels and recon of the two calls above bit for bit.  lambda is in
+ * 0..2^31-1; D < 2^43 and lambda * R < 2^42, so nothing wraps.
+ * d_modes, d_lvl, d_recon: the layouts of the two calls above (full blocks only;
+ * closed loop: recon 0 outside full blocks).  d_stats: three int64 per plane,
+ * planes in set order (sum J, sum D, sum R over the plane's blocks), OVERWRITTEN
+ * by the call -- zeroed on the stream first, so a plane with no full block gets
+ * 0, 0, 0.  block_size 8 runs here too, on the N-lane chains (the packed 8x8
+ * kernels have no rate term), which is why the closed form has a workspace-size
+ * call of its own: (w + 1) / 2 + N line words of 8 bytes per plane after two
+ * int32 words, 8-B aligned, zeroed by the call.  The closed form's status word is
+ * read with nh_intra_rdo_closed_status (0 ok, 1 a wavefront wait did not
+ * complete).  Both return NH_EARG on the host, before any HIP call (text in
+ * nh_last_error), for the cases nh_intra_rdo_planes_n refuses, a lambda outside
+ * 0..2^31-1, a null pointer (d_stats is required) and a d_stats or workspace
+ * that is not 8-B aligned; the workspace-size call returns a negative value for
+ * a refused case.  A call whose sets hold no plane returns 0 in the open form
+ * without touching the device. */
+int nh_intra_rdo_rd_planes_n(const int16_t* d_src, const nh_plane_set* sets, int nsets,
+                             int block_size, int use_dst, int qp, int64_t lambda,
+                             uint8_t* d_modes, int32_t* d_lvl, int16_t* d_recon,
+                             int64_t* d_stats, void* stream);
+int64_t nh_intra_rdo_rd_closed_n_workspace_bytes(const nh_plane_set* sets, int nsets,
+                                                 int block_size);
+int nh_intra_rdo_rd_planes_closed_n(const int16_t* d_src, const nh_plane_set* sets, int nsets,
+                                    int block_size, int use_dst, int qp, int64_t lambda,
+                                    uint8_t* d_modes, int32_t* d_lvl, int16_t* d_recon,
+                                    int64_t* d_stats, void* d_work, void* stream);
+
 /* ---- Closed-loop intra DECODER: modes + levels -> recon ----
  * Stage R: res = inverse_transform(dequantize_block(level, qp)).astype(int16)
  * (quant.py:82-123, transform.py:199-238, int32 wrap-around included) over every

@@ -37,6 +37,13 @@
 // The closed loop's DECODER at the same sizes (end of
 // the file): stage P, one prediction per block on the same row wavefront, after
 // stage R (nh_decode_n.hip) has put the residuals in place.
+//
+// Both loops with a RATE term: the kernels carry
+// a compile-time RD flag.  RD = true: the key is J = D + lambda * R with R =
+// count_nonzero(level) + 1 in place of the SSE, and (sum J, sum D, sum R) per
+// plane are accumulated.  The RD entry points serve N = 8 from the N-lane chains
+// as well.  RD = false is what the entry points without a rate term launch;
+// every RD statement is under `if constexpr`.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <climits>
@@ -65,7 +72,11 @@ struct RdoNArgs {
     int32_t vec_out;             // every row start of lvl / recon is 16-B aligned
     int64_t group_stride, plane_stride;
     int32_t ppg;
+    // the RD form (§3.3b) only: J = D + lambda * R, three words per plane (sum J, sum D, sum R)
+    unsigned long long lambda;
+    unsigned long long* stats;
 };
+constexpr int kRdoStats = 3;
 
 __device__ __forceinline__ int32_t w16(int32_t v) { return (int32_t)(int16_t)(uint16_t)(uint32_t)v; }
 
@@ -295,11 +306,24 @@ __device__ __forceinline__ unsigned long long lane_chain4(const RdoNBlock<4>& L,
 // ---------------------------------------------------------------------------
 // N = 4: lane = (block slot, mode)
 // ---------------------------------------------------------------------------
-template <bool DST>
+// nonzero levels of a 4x4 held in registers (the RD form's rate, §3.3b)
+__device__ __forceinline__ int32_t nnz4(const int32_t (&Lv)[4][4]) {
+    int32_t n = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) n += Lv[i][j] != 0;
+    return n;
+}
+
+// RD: the key is J = D + lambda * (nnz + 1) instead of the SSE, and the workgroup adds (sum J, sum D,
+// sum R) of its blocks to the plane's three stats words (§3.3b).
+template <bool DST, bool RD>
 __device__ __forceinline__ void rdo_n_lane(RdoNArgs a) {
     constexpr int N = 4;
     __shared__ RdoNBlock<N> B[kLaneSlots];
     __shared__ unsigned long long wg_sse;
+    __shared__ unsigned long long wg_dr[RD ? 2 : 1];   // RD: sum D, sum R of the workgroup
     const int bw = a.w / N, nblk = bw * (a.h / N);
     plane_offsets(a, nblk);
     const int t = threadIdx.x;
@@ -316,6 +340,9 @@ __device__ __forceinline__ void rdo_n_lane(RdoNArgs a) {
             }
         }
         if (t == 0) wg_sse = 0;
+        if constexpr (RD) {
+            if (t < 2) wg_dr[t] = 0;
+        }
     }
     __syncthreads();
     if (t < kLaneSlots && B[t].valid) B[t].dc = block_dc<N>(B[t]);
@@ -325,9 +352,15 @@ __device__ __forceinline__ void rdo_n_lane(RdoNArgs a) {
     const ChainQ cq = make_chainq(a.qp, a.dq_scale, a.dq_per);
     int32_t Lv[N][N];
     uint32_t Rp[N][N / 2];
-    unsigned long long key = ULLONG_MAX;
+    unsigned long long key = ULLONG_MAX, dist = 0, rate = 0;
     if (active) {
-        key = (lane_chain4<DST>(L, mode, cq, Lv, Rp) << 6) | (unsigned long long)mode;
+        dist = lane_chain4<DST>(L, mode, cq, Lv, Rp);
+        if constexpr (RD) {
+            rate = (unsigned long long)(nnz4(Lv) + 1);
+            key = ((dist + a.lambda * rate) << 6) | (unsigned long long)mode;
+        } else {
+            key = (dist << 6) | (unsigned long long)mode;
+        }
         atomicMin(&B[slot].best, key);
     }
     __syncthreads();
@@ -336,6 +369,10 @@ __device__ __forceinline__ void rdo_n_lane(RdoNArgs a) {
         const int by = b / bw, bx = b - by * bw;
         a.modes[b] = (uint8_t)mode;
         atomicAdd(&wg_sse, key >> 6);
+        if constexpr (RD) {
+            atomicAdd(&wg_dr[0], dist);
+            atomicAdd(&wg_dr[1], rate);
+        }
 #pragma unroll
         for (int i = 0; i < N; ++i) {
             const int64_t o = (int64_t)(by * N + i) * a.pitch + bx * N;
@@ -344,7 +381,11 @@ __device__ __forceinline__ void rdo_n_lane(RdoNArgs a) {
         }
     }
     __syncthreads();
-    if (a.sse && t == 0) atomicAdd(a.sse, wg_sse);   // once per workgroup
+    if constexpr (RD) {
+        if (t < kRdoStats) atomicAdd(a.stats + kRdoStats * (int64_t)blockIdx.y + t, t == 0 ? wg_sse : wg_dr[t - 1]);
+    } else {
+        if (a.sse && t == 0) atomicAdd(a.sse, wg_sse);   // once per workgroup
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -362,11 +403,11 @@ __device__ __forceinline__ void chain_sync() {
 // One (block, mode) chain on the N lanes of a chain: lane t does column t, then row t, through
 // the chain's LDS tile (pitch N + 1); rf: the chain's 3N + 2 angular reference samples.  Returns
 // the SSE of row t; rcp: row t of the recon as int16 pairs.  lvl_row (the winner's round): where
-// lane t stores row t of the levels, or null.
-template <int N>
+// lane t stores row t of the levels, or null.  RD: *nnz receives the nonzero levels of row t.
+template <int N, bool RD = false>
 __device__ __forceinline__ unsigned long long tile_chain(const RdoNBlock<N>& L, int mode, int t, int32_t (*tile)[N + 1],
                                                          int16_t* rf, const ChainQ& cq, int32_t* lvl_row, bool vec,
-                                                         uint32_t (&rcp)[N / 2]) {
+                                                         uint32_t (&rcp)[N / 2], int32_t* nnz = nullptr) {
     constexpr int S = Log2<N>::v + 5;
     int angle = 0;
     const bool vert = mode >= 18;
@@ -404,6 +445,12 @@ __device__ __forceinline__ unsigned long long tile_chain(const RdoNBlock<N>& L, 
             tile[t][j] = dequant_s(l[j], cq);
         }
         if (lvl_row) store_lvl_row<N>(lvl_row, l, vec);
+        if constexpr (RD) {
+            int32_t c = 0;
+#pragma unroll
+            for (int j = 0; j < N; ++j) c += l[j] != 0;
+            *nnz = c;
+        }
     }
     chain_sync();
     // inverse pass 1 on column t (this lane's own column)
@@ -432,7 +479,11 @@ __device__ __forceinline__ unsigned long long tile_chain(const RdoNBlock<N>& L, 
     return sse;
 }
 
-template <int N>
+// RD (§3.3b): a chain lane contributes sse_row + lambda * nnz_row, so the N-lane sum is D + lambda * nnz;
+// lane 0 of the chain adds lambda once.  The winner's round follows the loop: chain 0 of every block
+// sums the nonzero levels of its rerun (R = nnz + 1, J = best >> 6, D = J - lambda * R), and the
+// workgroup adds one (sum J, sum D, sum R) to the plane's stats words.
+template <int N, bool RD>
 __device__ __forceinline__ void rdo_n_tile(RdoNArgs a) {
     constexpr int BPW = 32 / N;                 // blocks per workgroup
     constexpr int NC = kChains * BPW;           // chains per workgroup
@@ -441,11 +492,15 @@ __device__ __forceinline__ void rdo_n_tile(RdoNArgs a) {
     __shared__ RdoNBlock<N> B[BPW];
     __shared__ int32_t tile[NC][N][P];
     __shared__ int16_t refs[NC][3 * N + 2];
+    __shared__ unsigned long long wg_st[RD ? kRdoStats : 1];
     const int bw = a.w / N, nblk = bw * (a.h / N);
     plane_offsets(a, nblk);
     const int tid = threadIdx.x;
     const int ci = tid / N, t = tid % N;
     const int blk = ci / kChains, c = ci - blk * kChains;
+    if constexpr (RD) {
+        if (tid < kRdoStats) wg_st[tid] = 0;    // ordered by the barriers of the staging below
+    }
     const int b0 = (int)blockIdx.x * BPW;
     for (int k = 0; k < BPW; ++k) {
         const int b = b0 + k;
@@ -469,6 +524,7 @@ __device__ __forceinline__ void rdo_n_tile(RdoNArgs a) {
         const bool emit = r == kModesN / kChains;      // the winner's round
         if (emit) {
             __syncthreads();                           // every chain's key is in L.best
+            if constexpr (RD) break;                   // the RD winner's round is below the loop
             if (tid == 0 && a.sse) {
                 unsigned long long s = 0;
                 for (int k = 0; k < BPW; ++k)
@@ -480,8 +536,11 @@ __device__ __forceinline__ void rdo_n_tile(RdoNArgs a) {
         if (!on) continue;
         const int mode = emit ? (int)(L.best & 63) : r * kChains + c;
         uint32_t rcp[N / 2];
-        unsigned long long sse = tile_chain<N>(L, mode, t, tile[ci], rf, cq,
-                                               emit ? a.lvl + (int64_t)(y0 + t) * a.pitch + x0 : nullptr, a.vec_out, rcp);
+        int32_t nnz = 0;
+        unsigned long long sse = tile_chain<N, RD>(L, mode, t, tile[ci], rf, cq,
+                                                   emit ? a.lvl + (int64_t)(y0 + t) * a.pitch + x0 : nullptr, a.vec_out,
+                                                   rcp, &nnz);
+        if constexpr (RD) sse += a.lambda * (unsigned long long)nnz;
         if (emit) {
             store_rec_row<N>(a.recon + (int64_t)(y0 + t) * a.pitch + x0, rcp, a.vec_out);
             if (t == 0) a.modes[b] = (uint8_t)mode;
@@ -490,14 +549,41 @@ __device__ __forceinline__ void rdo_n_tile(RdoNArgs a) {
         // the chain's SSE: sum over its N lanes (an aligned group of N lanes of the wave)
 #pragma unroll
         for (int m = N / 2; m >= 1; m >>= 1) sse += __shfl_xor(sse, m);
+        if constexpr (RD) sse += a.lambda;             // R = nnz + 1
         if (t == 0) atomicMin(&B[blk].best, (sse << 6) | (unsigned long long)mode);
         chain_sync();   // refs / tile are rewritten by the next round
     }
+    if constexpr (RD) {
+        if (on && c == 0) {
+            const unsigned long long best = L.best;
+            const int mode = (int)(best & 63);
+            uint32_t rcp[N / 2];
+            int32_t nnz = 0;
+            tile_chain<N, true>(L, mode, t, tile[ci], rf, cq, a.lvl + (int64_t)(y0 + t) * a.pitch + x0, a.vec_out, rcp,
+                                &nnz);
+            store_rec_row<N>(a.recon + (int64_t)(y0 + t) * a.pitch + x0, rcp, a.vec_out);
+#pragma unroll
+            for (int m = N / 2; m >= 1; m >>= 1) nnz += __shfl_xor(nnz, m);
+            if (t == 0) {
+                a.modes[b] = (uint8_t)mode;
+                const unsigned long long J = best >> 6, R = (unsigned long long)(nnz + 1);
+                atomicAdd(&wg_st[0], J);
+                atomicAdd(&wg_st[1], J - a.lambda * R);
+                atomicAdd(&wg_st[2], R);
+            }
+        }
+        __syncthreads();
+        // once per workgroup
+        if (tid < kRdoStats) atomicAdd(a.stats + kRdoStats * (int64_t)blockIdx.y + tid, wg_st[tid]);
+    }
 }
 
-template <int N, bool DST>
-__global__ void __launch_bounds__(N == 4 ? 256 : 224) k_intra_rdo_n(RdoNArgs a) {
-    if constexpr (N == 4) rdo_n_lane<DST>(a); else rdo_n_tile<N>(a);
+// The RD form at N = 32 needs 174 VGPRs where the plain form needs 144: held to the plain form's three
+// waves per SIMD (168 VGPRs, no scratch).  A bound of 1 is the default: the plain forms compile as before.
+template <int N, bool DST, bool RD = false>
+__global__ void __launch_bounds__(N == 4 ? 256 : 224) __attribute__((amdgpu_waves_per_eu(RD && N == 32 ? 3 : 1)))
+k_intra_rdo_n(RdoNArgs a) {
+    if constexpr (N == 4) rdo_n_lane<DST, RD>(a); else rdo_n_tile<N, RD>(a);
 }
 
 void split_qp(int qp, int log2n, QuantParams* q, int* per, int* rem) {
@@ -548,6 +634,7 @@ struct ClosedNArgs {
     int64_t lines_total;
     QuantParams qp;
     int32_t dq_scale, dq_per;
+    unsigned long long lambda;      // the RD form (§3.7b) only; sse then holds three words per plane
 };
 constexpr int kClosedNLines0 = 2;           // int32 words before the line words (8-B aligned)
 constexpr int kClosedNSpinLimit = 1 << 20;  // as kSpinLimit of the N = 8 kernel: ~1 s of polling
@@ -634,8 +721,11 @@ __device__ __forceinline__ void closed_stage_refs(RdoNBlock<N>& B, int k, const 
 }
 
 // N = 4: one wave per block row, a lane per mode, the block in registers (lane_chain4).
-template <bool DST>
-__global__ void __launch_bounds__(64) k_intra_rdo_closed_lane(ClosedNArgs a) {
+// RD (§3.7b): the key is J = D + lambda * (nnz + 1), and the row adds (sum J, sum D, sum R) to its plane's
+// three words at a.sse.
+template <bool DST, bool RD = false>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RD ? 4 : 1)))   // RD: 128 VGPRs as the plain form
+k_intra_rdo_closed_lane(ClosedNArgs a) {
     constexpr int N = 4;
     __shared__ RdoNBlock<N> B;
     __shared__ uint32_t topw[N];
@@ -657,7 +747,7 @@ __global__ void __launch_bounds__(64) k_intra_rdo_closed_lane(ClosedNArgs a) {
         const ClosedNRow R = closed_row(a, S, pl, by);
         const int y0 = by * N, full_words = S.bw * (N / 2);
         int16_t tl_next = 128;
-        unsigned long long row_sse = 0;
+        unsigned long long row_sse = 0, row_d = 0, row_r = 0;   // row_d, row_r: RD only
         for (int bx = 0; bx < S.bw; ++bx) {
             const int x0 = bx * N;
             int16_t ov = 0;
@@ -677,8 +767,16 @@ __global__ void __launch_bounds__(64) k_intra_rdo_closed_lane(ClosedNArgs a) {
             __syncthreads();
             int32_t Lv[N][N];
             uint32_t Rp[N][N / 2];
-            unsigned long long key = ULLONG_MAX;
-            if (lane < kModesN) key = (lane_chain4<DST>(B, lane, cq, Lv, Rp) << 6) | (unsigned long long)lane;
+            unsigned long long key = ULLONG_MAX, dist = 0, rate = 0;
+            if (lane < kModesN) {
+                dist = lane_chain4<DST>(B, lane, cq, Lv, Rp);
+                if constexpr (RD) {
+                    rate = (unsigned long long)(nnz4(Lv) + 1);
+                    key = ((dist + a.lambda * rate) << 6) | (unsigned long long)lane;
+                } else {
+                    key = (dist << 6) | (unsigned long long)lane;
+                }
+            }
             unsigned long long best = key;
 #pragma unroll
             for (int m = 32; m >= 1; m >>= 1) {
@@ -699,12 +797,27 @@ __global__ void __launch_bounds__(64) k_intra_rdo_closed_lane(ClosedNArgs a) {
                 }
                 R.modes[bx] = (uint8_t)lane;
                 row_sse += best >> 6;
+                if constexpr (RD) {
+                    row_d += dist;
+                    row_r += rate;
+                }
             }
             __syncthreads();   // leftcol is there; B is free for the next block
         }
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1) row_sse += __shfl_xor(row_sse, m);
-        if (lane == 0 && row_sse) atomicAdd(&a.sse[S.plane0 + pl], row_sse);
+        if constexpr (RD) {
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) {
+                row_d += __shfl_xor(row_d, m);
+                row_r += __shfl_xor(row_r, m);
+            }
+            if (lane < kRdoStats && row_r)
+                atomicAdd(&a.sse[kRdoStats * (int64_t)(S.plane0 + pl) + lane],
+                          lane == 0 ? row_sse : lane == 1 ? row_d : row_r);
+        } else {
+            if (lane == 0 && row_sse) atomicAdd(&a.sse[S.plane0 + pl], row_sse);
+        }
         const int stalled = stall_s;
         __syncthreads();       // before lane 0 resets stall_s for the next row
         if (stalled) break;
@@ -716,8 +829,11 @@ __global__ void __launch_bounds__(64) k_intra_rdo_closed_lane(ClosedNArgs a) {
 // runs the winner once more and stores its levels and recon.  Wave 0 polls; the words and the
 // stall flag reach the others through LDS and a workgroup barrier.  Every thread passes the same
 // barriers: the stall exit is taken by all of them after the same barrier.
-template <int N>
-__global__ void __launch_bounds__(224) k_intra_rdo_closed_tile(ClosedNArgs a) {
+// RD (§3.7b): the chains' keys as in rdo_n_tile's RD form; chain 0 sums the nonzero levels of the winner's
+// rerun, and thread 0 adds the row's (sum J, sum D, sum R) to its plane's three words at a.sse.
+template <int N, bool RD = false>
+__global__ void __launch_bounds__(224) __attribute__((amdgpu_waves_per_eu(RD && N == 16 ? 4 : 1)))   // <= 128 VGPRs
+k_intra_rdo_closed_tile(ClosedNArgs a) {
     constexpr int NT = 224, NC = NT / N, ROUNDS = (kModesN + NC - 1) / NC, P = N + 1;
     constexpr int OV = (N * N + NT - 1) / NT;   // source samples per thread
     static_assert(3 * N + 1 <= NT && N <= 64, "neighbour staging and the poll need that many threads");
@@ -745,6 +861,7 @@ __global__ void __launch_bounds__(224) k_intra_rdo_closed_tile(ClosedNArgs a) {
         const int y0 = by * N, full_words = S.bw * (N / 2);
         int16_t tl_next = 128;              // thread 3N's
         unsigned long long row_sse = 0;     // thread 0's
+        unsigned long long row_d = 0, row_r = 0;   // thread 0's, RD only
         for (int bx = 0; bx < S.bw; ++bx) {
             const int x0 = bx * N;
             int16_t ov[OV];
@@ -774,10 +891,14 @@ __global__ void __launch_bounds__(224) k_intra_rdo_closed_tile(ClosedNArgs a) {
                 const int mode = r * NC + ci;
                 if (mode < kModesN) {
                     uint32_t rcp[N / 2];
-                    unsigned long long sse = tile_chain<N>(B, mode, t, tile[ci], refs[ci], cq, nullptr, false, rcp);
+                    int32_t nnz = 0;
+                    unsigned long long sse =
+                        tile_chain<N, RD>(B, mode, t, tile[ci], refs[ci], cq, nullptr, false, rcp, &nnz);
+                    if constexpr (RD) sse += a.lambda * (unsigned long long)nnz;
                     // the chain's SSE: sum over its N lanes (an aligned group of N lanes of the wave)
 #pragma unroll
                     for (int m = N / 2; m >= 1; m >>= 1) sse += __shfl_xor(sse, m);
+                    if constexpr (RD) sse += a.lambda;   // R = nnz + 1
                     if (t == 0) atomicMin(&B.best, (sse << 6) | (unsigned long long)mode);
                     chain_sync();           // refs / tile are rewritten by the next round
                 }
@@ -788,7 +909,8 @@ __global__ void __launch_bounds__(224) k_intra_rdo_closed_tile(ClosedNArgs a) {
                 const int mode = (int)(best & 63);
                 const int64_t o = (int64_t)(y0 + t) * S.pitch + x0;
                 uint32_t rcp[N / 2];
-                tile_chain<N>(B, mode, t, tile[0], refs[0], cq, R.lvl + o, S.vec_out != 0, rcp);
+                int32_t nnz = 0;
+                tile_chain<N, RD>(B, mode, t, tile[0], refs[0], cq, R.lvl + o, S.vec_out != 0, rcp, &nnz);
                 if (t == N - 1) {           // publish the bottom row first (the next row polls these words)
                     const uint64_t tag = (uint64_t)(uint32_t)(by + 1) << 32;
 #pragma unroll
@@ -796,14 +918,32 @@ __global__ void __launch_bounds__(224) k_intra_rdo_closed_tile(ClosedNArgs a) {
                 }
                 leftcol[t] = (int16_t)(rcp[N / 2 - 1] >> 16);
                 store_rec_row<N>(R.rec + o, rcp, S.vec_out != 0);
+                if constexpr (RD) {
+#pragma unroll
+                    for (int m = N / 2; m >= 1; m >>= 1) nnz += __shfl_xor(nnz, m);
+                }
                 if (t == 0) {
                     R.modes[bx] = (uint8_t)mode;
                     row_sse += best >> 6;
+                    if constexpr (RD) {
+                        const unsigned long long r = (unsigned long long)(nnz + 1);
+                        row_d += (best >> 6) - a.lambda * r;
+                        row_r += r;
+                    }
                 }
             }
             __syncthreads();                // leftcol is there; B, topw are free for the next block
         }
-        if (tid == 0 && row_sse) atomicAdd(&a.sse[S.plane0 + pl], row_sse);
+        if constexpr (RD) {
+            if (tid == 0 && row_r) {
+                unsigned long long* st = &a.sse[kRdoStats * (int64_t)(S.plane0 + pl)];
+                atomicAdd(st, row_sse);
+                atomicAdd(st + 1, row_d);
+                atomicAdd(st + 2, row_r);
+            }
+        } else {
+            if (tid == 0 && row_sse) atomicAdd(&a.sse[S.plane0 + pl], row_sse);
+        }
         const int stalled = stall_s;
         __syncthreads();                    // before thread 0 resets stall_s for the next row
         if (stalled) break;
@@ -1267,6 +1407,170 @@ extern "C" int nh_intra_decode_planes_closed_n(const uint8_t* d_modes, const int
         if (N == 4) NH_TRY(launch_closed_n(k_intra_dec_closed_n<4>, 64, a, s));
         else if (N == 16) NH_TRY(launch_closed_n(k_intra_dec_closed_n<16>, 64, a, s));
         else NH_TRY(launch_closed_n(k_intra_dec_closed_n<32>, 64, a, s));
+    }
+    return NH_OK;
+}
+
+// ===========================================================================
+// The RD forms: the kernels above with RD = true, at
+// N = 4, 8, 16 and 32 -- N = 8 on the N-lane chains too (4 blocks per workgroup
+// in the open loop, 28 chains over 2 rounds in the closed loop).
+// ===========================================================================
+namespace nh {
+namespace {
+
+// The refusals the two RD entry points add to check_rdo_n_args'.
+int check_rd_args(const char* who, const nh_plane_set* sets, int nsets, int block_size, int use_dst, int qp,
+                  int64_t lambda, const void* d_stats) {
+    NH_TRY(check_rdo_n_args(who, sets, nsets, block_size, use_dst, qp));
+    if (lambda < 0 || lambda > 0x7fffffffll) {
+        set_error(std::string(who) + ": lambda outside 0..2^31-1");
+        return NH_EARG;
+    }
+    if ((uintptr_t)d_stats & 7) {
+        set_error(std::string(who) + ": d_stats must be 8-byte aligned");
+        return NH_EARG;
+    }
+    return NH_OK;
+}
+
+int64_t planes_of(const nh_plane_set* sets, int nsets) {
+    int64_t n = 0;
+    for (int k = 0; k < nsets; ++k) n += (int64_t)sets[k].planes_per_group * sets[k].num_groups;
+    return n;
+}
+
+int log2_of(int n) { return n == 4 ? 2 : n == 8 ? 3 : n == 16 ? 4 : 5; }
+
+}  // namespace
+}  // namespace nh
+
+extern "C" int nh_intra_rdo_rd_planes_n(const int16_t* d_src, const nh_plane_set* sets, int nsets, int block_size,
+                                        int use_dst, int qp, int64_t lambda, uint8_t* d_modes, int32_t* d_lvl,
+                                        int16_t* d_recon, int64_t* d_stats, void* stream) {
+    if (!d_src || !sets || !d_modes || !d_lvl || !d_recon || !d_stats) {
+        set_error("nh_intra_rdo_rd_planes_n: null argument");
+        return NH_EARG;
+    }
+    NH_TRY(check_rd_args("nh_intra_rdo_rd_planes_n", sets, nsets, block_size, use_dst, qp, lambda, d_stats));
+    const int64_t total_planes = planes_of(sets, nsets);
+    if (!total_planes) return NH_OK;   // nothing to code, no stats word to zero
+
+    const int N = block_size;
+    RdoNArgs a{};
+    int per, rem;
+    split_qp(qp, log2_of(N), &a.qp, &per, &rem);
+    a.dq_scale = dequant_scale(rem);
+    a.dq_per = per;
+    a.lambda = (unsigned long long)lambda;
+    const hipStream_t s = as_stream(stream);
+    NH_HIP(hipMemsetAsync(d_stats, 0, 8ull * kRdoStats * (uint64_t)total_planes, s));
+    int64_t moff = 0, soff = 0;
+    for (int k = 0; k < nsets; ++k) {
+        const nh_plane_set& S = sets[k];
+        const int64_t planes = (int64_t)S.planes_per_group * S.num_groups;
+        const int nblk = (S.width / N) * (S.height / N);
+        if (nblk && planes) {
+            a.src = d_src + S.base;
+            a.lvl = d_lvl + S.base;
+            a.recon = d_recon + S.base;
+            a.modes = d_modes + moff;
+            a.sse = nullptr;
+            a.stats = (unsigned long long*)(d_stats + kRdoStats * soff);
+            a.w = S.width;
+            a.h = S.height;
+            a.pitch = S.pitch;
+            a.vec_out = !(S.pitch & 7) && !((S.base | S.plane_stride | S.group_stride) & 7) &&
+                        !((uintptr_t)d_lvl & 15) && !((uintptr_t)d_recon & 15);
+            a.group_stride = S.group_stride;
+            a.plane_stride = S.plane_stride;
+            a.ppg = S.planes_per_group;
+            const unsigned py = (unsigned)planes;
+            if (N == 4) {
+                const dim3 grid((unsigned)((nblk + kLaneSlots - 1) / kLaneSlots), py);
+                if (use_dst) k_intra_rdo_n<4, true, true><<<grid, 256, 0, s>>>(a);
+                else k_intra_rdo_n<4, false, true><<<grid, 256, 0, s>>>(a);
+            } else if (N == 8) {
+                k_intra_rdo_n<8, false, true><<<dim3((unsigned)((nblk + 3) / 4), py), 224, 0, s>>>(a);
+            } else if (N == 16) {
+                k_intra_rdo_n<16, false, true><<<dim3((unsigned)((nblk + 1) / 2), py), 224, 0, s>>>(a);
+            } else {
+                k_intra_rdo_n<32, false, true><<<dim3((unsigned)nblk, py), 224, 0, s>>>(a);
+            }
+            NH_HIP(hipGetLastError());
+        }
+        moff += planes * nblk;
+        soff += planes;
+    }
+    return NH_OK;
+}
+
+extern "C" int64_t nh_intra_rdo_rd_closed_n_workspace_bytes(const nh_plane_set* sets, int nsets, int block_size) {
+    if (!sets) {
+        set_error("nh_intra_rdo_rd_closed_n_workspace_bytes: null argument");
+        return -1;
+    }
+    if (check_rdo_n_args("nh_intra_rdo_rd_closed_n_workspace_bytes", sets, nsets, block_size, 0, 0)) return -1;
+    ClosedNArgs a;
+    if (closed_n_layout(sets, nsets, block_size, a)) {
+        set_error("nh_intra_rdo_rd_closed_n_workspace_bytes: bad plane set (sizes <= 65535, < 2^30 block rows)");
+        return -1;
+    }
+    return 4ll * kClosedNLines0 + 8ll * a.lines_total;
+}
+
+extern "C" int nh_intra_rdo_rd_planes_closed_n(const int16_t* d_src, const nh_plane_set* sets, int nsets,
+                                               int block_size, int use_dst, int qp, int64_t lambda, uint8_t* d_modes,
+                                               int32_t* d_lvl, int16_t* d_recon, int64_t* d_stats, void* d_work,
+                                               void* stream) {
+    if (!d_src || !sets || !d_modes || !d_lvl || !d_recon || !d_stats || !d_work) {
+        set_error("nh_intra_rdo_rd_planes_closed_n: null argument");
+        return NH_EARG;
+    }
+    NH_TRY(check_rd_args("nh_intra_rdo_rd_planes_closed_n", sets, nsets, block_size, use_dst, qp, lambda, d_stats));
+    const int N = block_size;
+    ClosedNArgs a{};
+    if (closed_n_layout(sets, nsets, N, a)) {
+        set_error("nh_intra_rdo_rd_planes_closed_n: bad plane set (sizes <= 65535, < 2^30 block rows)");
+        return NH_EARG;
+    }
+    if ((uintptr_t)d_work & 7) {
+        set_error("nh_intra_rdo_rd_planes_closed_n: workspace must be 8-byte aligned");
+        return NH_EARG;
+    }
+    int per, rem;
+    split_qp(qp, log2_of(N), &a.qp, &per, &rem);
+    a.dq_scale = dequant_scale(rem);
+    a.dq_per = per;
+    a.lambda = (unsigned long long)lambda;
+    a.src = d_src;
+    a.lvl = d_lvl;
+    a.rec = d_recon;
+    a.modes = d_modes;
+    a.sse = (unsigned long long*)d_stats;   // three words per plane in the RD kernels
+    a.work = (int32_t*)d_work;
+    const bool aligned = !((uintptr_t)d_lvl & 15) && !((uintptr_t)d_recon & 15);
+    const hipStream_t s = as_stream(stream);
+    NH_HIP(hipMemsetAsync(d_work, 0, 4ull * kClosedNLines0 + 8ull * a.lines_total, s));
+    const int64_t total_planes = planes_of(sets, nsets);
+    if (total_planes) NH_HIP(hipMemsetAsync(d_stats, 0, 8ull * kRdoStats * (uint64_t)total_planes, s));
+    for (int k = 0; k < nsets; ++k) {
+        a.set[k].vec_out = a.set[k].vec_out && aligned;
+        if (a.set[k].np > 0 && (int64_t)a.set[k].w * a.set[k].h > 0)
+            k_zero_partial_n<<<dim3(64, (unsigned)a.set[k].np), 256, 0, s>>>(d_recon, a.set[k], N);
+    }
+    NH_HIP(hipGetLastError());
+    if (a.total_rows > 0) {
+        if (N == 4) {
+            if (use_dst) NH_TRY(launch_closed_n(k_intra_rdo_closed_lane<true, true>, 64, a, s));
+            else NH_TRY(launch_closed_n(k_intra_rdo_closed_lane<false, true>, 64, a, s));
+        } else if (N == 8) {
+            NH_TRY(launch_closed_n(k_intra_rdo_closed_tile<8, true>, 224, a, s));
+        } else if (N == 16) {
+            NH_TRY(launch_closed_n(k_intra_rdo_closed_tile<16, true>, 224, a, s));
+        } else {
+            NH_TRY(launch_closed_n(k_intra_rdo_closed_tile<32, true>, 224, a, s));
+        }
     }
     return NH_OK;
 }

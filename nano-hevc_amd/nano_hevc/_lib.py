@@ -94,6 +94,9 @@ SIGNATURES = {
     "nh_intra_rdo_closed_status": ([P, P, VP], I32),
     "nh_intra_rdo_closed_n_workspace_bytes": ([C.POINTER(PlaneSet), I32, I32], I64),
     "nh_intra_rdo_planes_closed_n": ([P, C.POINTER(PlaneSet), I32, I32, I32, I32, P, P, P, P, P, VP], I32),
+    "nh_intra_rdo_rd_planes_n": ([P, C.POINTER(PlaneSet), I32, I32, I32, I32, I64, P, P, P, P, VP], I32),
+    "nh_intra_rdo_rd_closed_n_workspace_bytes": ([C.POINTER(PlaneSet), I32, I32], I64),
+    "nh_intra_rdo_rd_planes_closed_n": ([P, C.POINTER(PlaneSet), I32, I32, I32, I32, I64, P, P, P, P, P, VP], I32),
     "nh_dequant_inv8x8_planes": ([P, I32, P, C.POINTER(PlaneSet), I32, I32, VP], I32),
     "nh_intra_decode_closed_workspace_bytes": ([C.POINTER(PlaneSet), I32], I64),
     "nh_intra_decode_planes_closed": ([P, P, C.POINTER(PlaneSet), I32, I32, P, P, VP], I32),

@@ -452,6 +452,111 @@ def intra_rdo_closed_n(src, sets: Sequence[PlaneSet], block_size: int, qp: int =
     return modes[:nmodes], lvl, rec, sse[:nplanes]
 
 
+def _rdo_rd_prepare(src, sets: Sequence[PlaneSet], block_size: int, lam: int, lvl, rec, what: str):
+    """Argument checks and default outputs shared by the open and the closed RD form
+    (DESIGN.md §3.3b, §3.7b); returns (n, lvl, rec, modes, stats, nmodes, nplanes)."""
+    torch = _torch()
+    _need(src, torch.int16, f"{what}(src)")
+    n = int(block_size)
+    if n not in (4, 8, 16, 32):
+        raise ValueError(f"{what}: block_size must be 4, 8, 16 or 32, got {block_size}")
+    if not 0 <= int(lam) <= 2 ** 31 - 1:
+        raise ValueError(f"{what}: lam (lambda) must be in 0..2^31-1")
+    sets_fit(sets, src.numel(), what)
+    nmodes = sum((s.width // n) * (s.height // n) * s.planes_per_group * s.num_groups for s in sets)
+    nplanes = sum(s.planes_per_group * s.num_groups for s in sets)
+    dev = src.device
+    if lvl is None:
+        lvl = torch.zeros(src.shape, dtype=torch.int32, device=dev)
+    if rec is None:
+        rec = torch.zeros(src.shape, dtype=torch.int16, device=dev)
+    _need(lvl, torch.int32, f"{what}(lvl)")
+    _need(rec, torch.int16, f"{what}(rec)")
+    if lvl.numel() < src.numel() or rec.numel() < src.numel():
+        raise ValueError(f"{what}: lvl / rec smaller than src")
+    modes = torch.zeros(max(1, nmodes), dtype=torch.uint8, device=dev)
+    stats = torch.empty((max(1, nplanes), 3), dtype=torch.int64, device=dev)   # overwritten by the call
+    return n, lvl, rec, modes, stats, nmodes, nplanes
+
+
+def intra_rdo_rd_planes_n(src, sets: Sequence[PlaneSet], block_size: int, qp: int = 32, lam: int = 0,
+                          use_dst: bool = False, lvl=None, rec=None, stream=None):
+    """Config 3 with a rate term, open loop, at block size N =
+    ``block_size`` in {4, 8, 16, 32} over every plane of ``sets``: the 35 chains of
+    ``intra_rdo_planes_n`` per full NxN block, the winner by J = D + lam * R with
+    D = sum (int16)(orig - rec)^2 and R = count_nonzero(level) + 1 (the rate of
+    ``tu_rd_planes``), ties to the lowest mode.  ``lam`` 0..2^31-1; ``lam`` = 0 gives
+    ``intra_rdo_planes_n``'s modes, levels and recon.  Returns (modes uint8 [sum of
+    per-plane (h/N)*(w/N), set order], lvl int32, recon int16 (source layout;
+    samples outside full blocks keep the caller's contents), stats int64
+    (planes, 3): sum J, sum D, sum R over the plane's blocks, overwritten).  Bad
+    arguments raise ValueError (a QP outside 0..51 is not clamped).  N = 8 runs the
+    N-lane chains, not the packed ``intra_rdo_planes`` kernels."""
+    what = "intra_rdo_rd_planes_n"
+    n, lvl, rec, modes, stats, nmodes, nplanes = _rdo_rd_prepare(src, sets, block_size, lam, lvl, rec, what)
+    arr = (PlaneSet * max(1, len(sets)))(*sets)
+    check(_lib.load().nh_intra_rdo_rd_planes_n(src.data_ptr(), arr, len(sets), n, int(bool(use_dst)), int(qp), int(lam),
+                                               modes.data_ptr(), lvl.data_ptr(), rec.data_ptr(), stats.data_ptr(),
+                                               C.c_void_p(_stream(stream, src.device))), what)
+    return modes[:nmodes], lvl, rec, stats[:nplanes]
+
+
+def intra_rdo_rd_plane_n(src2d, block_size: int, qp: int = 32, lam: int = 0, use_dst: bool = False,
+                         pitch: int | None = None, stream=None):
+    """``intra_rdo_rd_planes_n`` on one int16 plane (H, W) whose rows are ``pitch``
+    (default W) samples apart: (modes u8 (H/N, W/N), levels int32 (H, W), recon int16
+    (H, W), stats int64 (1, 3))."""
+    torch = _torch()
+    _need(src2d, torch.int16, "intra_rdo_rd_plane_n")
+    h, w = src2d.shape
+    p = int(pitch or w)
+    if p != w:   # rows of the (H, W) tensor re-spaced: run on a pitched copy, return (H, W) views
+        if p < w:
+            raise ValueError("intra_rdo_rd_plane_n: pitch < width")
+        buf = torch.zeros((h, p), dtype=torch.int16, device=src2d.device)
+        buf[:, :w] = src2d
+        modes, lvl, rec, stats = intra_rdo_rd_planes_n(buf, [plane_set(0, w, h, p)], block_size, qp, lam, use_dst,
+                                                       stream=stream)
+        lvl, rec = lvl[:, :w], rec[:, :w]
+    else:
+        modes, lvl, rec, stats = intra_rdo_rd_planes_n(src2d, [plane_set(0, w, h, w)], block_size, qp, lam, use_dst,
+                                                       stream=stream)
+    n = int(block_size)
+    return modes.reshape(h // n, w // n), lvl, rec, stats
+
+
+def intra_rdo_rd_closed_n(src, sets: Sequence[PlaneSet], block_size: int, qp: int = 32, lam: int = 0,
+                          use_dst: bool = False, lvl=None, rec=None, stream=None):
+    """Config 3 with a rate term in CLOSED loop: ``intra_rdo_closed_n``
+    with the winner of every block chosen by J = D + lam * R (as
+    ``intra_rdo_rd_planes_n``); the neighbours of later blocks come from the J
+    winner's reconstruction, and ``intra_decode_closed_n(modes, lvl, ...)`` returns
+    ``rec``.  ``lam`` = 0 gives ``intra_rdo_closed_n``'s modes, levels and recon.
+    Returns (modes, lvl int32 (samples outside full blocks keep the caller's
+    contents), recon int16 (0 outside full blocks), stats int64 (planes, 3): sum J,
+    sum D, sum R, overwritten).  Bad arguments raise ValueError; a stalled wavefront
+    raises RuntimeError."""
+    what = "intra_rdo_rd_closed_n"
+    n, lvl, rec, modes, stats, nmodes, nplanes = _rdo_rd_prepare(src, sets, block_size, lam, lvl, rec, what)
+    torch = _torch()
+    dev = src.device
+    L = _lib.load()
+    arr = (PlaneSet * max(1, len(sets)))(*sets)
+    wb = int(L.nh_intra_rdo_rd_closed_n_workspace_bytes(arr, len(sets), n))
+    if wb < 0:
+        raise ValueError(f"{what}: bad argument: " + L.nh_last_error().decode(errors="replace"))
+    work = torch.empty(max(2, (wb + 7) // 8 * 2), dtype=torch.int32, device=dev)
+    st = C.c_void_p(_stream(stream, dev))
+    check(L.nh_intra_rdo_rd_planes_closed_n(src.data_ptr(), arr, len(sets), n, int(bool(use_dst)), int(qp), int(lam),
+                                            modes.data_ptr(), lvl.data_ptr(), rec.data_ptr(), stats.data_ptr(),
+                                            work.data_ptr(), st), what)
+    status = C.c_int(0)
+    check(L.nh_intra_rdo_closed_status(work.data_ptr(), C.byref(status), st))
+    if status.value:
+        raise RuntimeError(f"{what}: the wavefront stalled (device status word set)")
+    return modes[:nmodes], lvl, rec, stats[:nplanes]
+
+
 def dequant_inv8x8(lvl, sets: Sequence[PlaneSet], qp: int = 32, out=None, stream=None):
     """Stage R of the decoder, the mirror of ``fwd8x8_quant``:
     inverse_transform(dequantize_block(level, qp)).astype(int16) on every full
