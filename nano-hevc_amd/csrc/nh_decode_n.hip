@@ -168,7 +168,8 @@ __global__ void __launch_bounds__(256) k_dequant_inv_n(DeqNArgs a) {
 
 }  // namespace
 
-int check_decode_n_args(const char* who, const nh_plane_set* sets, int nsets, int block_size, int use_dst) {
+int check_rdo_n_args(const char* who, const nh_plane_set* sets, int nsets, int block_size, int use_dst, int qp,
+                     bool check_qp) {
     const std::string w(who);
     if (block_size != 4 && block_size != 8 && block_size != 16 && block_size != 32) {
         set_error(w + ": block_size must be 4, 8, 16 or 32");
@@ -176,6 +177,10 @@ int check_decode_n_args(const char* who, const nh_plane_set* sets, int nsets, in
     }
     if (use_dst && block_size != 4) {
         set_error(w + ": use_dst needs block_size 4 (transform.py:138-141)");
+        return NH_EARG;
+    }
+    if (check_qp && (qp < 0 || qp > 51)) {
+        set_error(w + ": qp outside 0..51");
         return NH_EARG;
     }
     if (nsets < 1 || nsets > NH_MAX_PLANE_SETS) {
@@ -204,7 +209,7 @@ extern "C" int nh_dequant_inv_planes_n(const void* d_lvl, int lvl_bytes, int16_t
         set_error("nh_dequant_inv_planes_n: null argument");
         return NH_EARG;
     }
-    NH_TRY(check_decode_n_args("nh_dequant_inv_planes_n", sets, nsets, block_size, use_dst));
+    NH_TRY(check_rdo_n_args("nh_dequant_inv_planes_n", sets, nsets, block_size, use_dst, qp, false));
     if (lvl_bytes != 2 && lvl_bytes != 4) {
         set_error("nh_dequant_inv_planes_n: lvl_bytes must be 2 (int16) or 4 (int32)");
         return NH_EARG;
@@ -218,7 +223,7 @@ extern "C" int nh_dequant_inv_planes_n(const void* d_lvl, int lvl_bytes, int16_t
     DeqNArgs a{};
     a.lvl = d_lvl;
     a.res = d_res;
-    a.log2n = N == 4 ? 2 : N == 16 ? 4 : 5;
+    a.log2n = log2_of(N);
     a.dst = use_dst ? 1 : 0;
     bool aligned = !((uintptr_t)d_lvl & 15) && !((uintptr_t)d_res & 15);
     uint64_t wg = 0;

@@ -6,8 +6,12 @@
 
 namespace nh {
 
-// The decoder's refusals: the closed encoder's (check_rdo_n_args, nh_rdo_n.hip)
-// minus QP, which a decoder clamps to 0..51 instead.  `who` names the caller.
-int check_decode_n_args(const char* who, const nh_plane_set* sets, int nsets, int block_size, int use_dst);
+// The refusals every entry point at a block size N shares, in this order: block
+// size, use_dst, QP outside 0..51, nsets, plane set.  A decoder clamps QP to
+// 0..51 instead and passes check_qp = false.  `who` names the caller.
+int check_rdo_n_args(const char* who, const nh_plane_set* sets, int nsets, int block_size, int use_dst, int qp,
+                     bool check_qp = true);
+
+inline int log2_of(int n) { return n == 4 ? 2 : n == 8 ? 3 : n == 16 ? 4 : 5; }   // of a block size that passed the check
 
 }  // namespace nh

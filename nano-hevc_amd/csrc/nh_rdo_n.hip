@@ -34,8 +34,8 @@
 // wavefront of the N = 8 closed loop.  Its residual is int16 whatever the
 // prediction, so the operand bounds above hold for it as they are.
 //
-// The closed loop's DECODER at the same sizes (end of
-// the file): stage P, one prediction per block on the same row wavefront, after
+// The closed loop's DECODER at the same sizes (the last
+// kernel): stage P, one prediction per block on the same row wavefront, after
 // stage R (nh_decode_n.hip) has put the residuals in place.
 //
 // Both loops with a RATE term: the kernels carry
@@ -962,46 +962,40 @@ __global__ void __launch_bounds__(256) k_zero_partial_n(int16_t* rec, ClosedNSet
     }
 }
 
-// The argument checks shared by the open- and the closed-loop entry points; `who` names the caller.
-int check_rdo_n_args(const char* who, const nh_plane_set* sets, int nsets, int block_size, int use_dst, int qp) {
-    const std::string w(who);
-    if (block_size != 4 && block_size != 8 && block_size != 16 && block_size != 32) {
-        set_error(w + ": block_size must be 4, 8, 16 or 32");
+// The refusals the two RD entry points add to check_rdo_n_args' (nh_decode_n.hip); `who` names the caller.
+int check_rd_args(const char* who, const nh_plane_set* sets, int nsets, int block_size, int use_dst, int qp,
+                  int64_t lambda, const void* d_stats) {
+    NH_TRY(check_rdo_n_args(who, sets, nsets, block_size, use_dst, qp));
+    if (lambda < 0 || lambda > 0x7fffffffll) {
+        set_error(std::string(who) + ": lambda outside 0..2^31-1");
         return NH_EARG;
     }
-    if (use_dst && block_size != 4) {
-        set_error(w + ": use_dst needs block_size 4 (transform.py:138-141)");
+    if ((uintptr_t)d_stats & 7) {
+        set_error(std::string(who) + ": d_stats must be 8-byte aligned");
         return NH_EARG;
-    }
-    if (qp < 0 || qp > 51) {
-        set_error(w + ": qp outside 0..51");
-        return NH_EARG;
-    }
-    if (nsets < 1 || nsets > NH_MAX_PLANE_SETS) {
-        set_error(w + ": nsets outside 1..8");
-        return NH_EARG;
-    }
-    for (int k = 0; k < nsets; ++k) {
-        const nh_plane_set& S = sets[k];
-        const int64_t planes = (int64_t)S.planes_per_group * S.num_groups;
-        if (S.width < 0 || S.height < 0 || S.pitch < S.width || S.planes_per_group < 1 || S.num_groups < 0 ||
-            planes > 65535 || S.base < 0 || S.plane_stride < 0 || S.group_stride < 0) {
-            set_error(w + ": bad plane set");
-            return NH_EARG;
-        }
     }
     return NH_OK;
 }
 
+int64_t planes_of(const nh_plane_set* sets, int nsets) {
+    int64_t n = 0;
+    for (int k = 0; k < nsets; ++k) n += (int64_t)sets[k].planes_per_group * sets[k].num_groups;
+    return n;
+}
+
 // Rows, planes, mode-map and line-word offsets of the closed loop at block size n.  The sets have
-// passed check_rdo_n_args' plane-set test.  NH_EARG: a plane wider or higher than 65535 samples,
-// or 2^30 block rows and more.
-int closed_n_layout(const nh_plane_set* sets, int nsets, int n, ClosedNArgs& a) {
+// passed check_rdo_n_args' plane-set test.  NH_EARG, with `who` in the error text: a plane wider or
+// higher than 65535 samples, or 2^30 block rows and more.
+int closed_n_layout(const char* who, const nh_plane_set* sets, int nsets, int n, ClosedNArgs& a) {
+    const auto refuse = [who] {
+        set_error(std::string(who) + ": bad plane set (sizes <= 65535, < 2^30 block rows)");
+        return NH_EARG;
+    };
     int64_t rows = 0, planes = 0, modes = 0, lines = 0;
     a.max_bh = 0;
     for (int k = 0; k < nsets; ++k) {
         const nh_plane_set& p = sets[k];
-        if (p.width > 65535 || p.height > 65535) return NH_EARG;
+        if (p.width > 65535 || p.height > 65535) return refuse();
         ClosedNSet& S = a.set[k];
         S.base = p.base;
         S.plane_stride = p.plane_stride;
@@ -1025,7 +1019,7 @@ int closed_n_layout(const nh_plane_set* sets, int nsets, int n, ClosedNArgs& a) 
         planes += np;
         modes += np * (p.width / n) * (p.height / n);
         lines += np * S.lw;
-        if (rows >= (1ll << 30)) return NH_EARG;
+        if (rows >= (1ll << 30)) return refuse();
     }
     a.nsets = nsets;
     a.total_rows = (int32_t)rows;
@@ -1052,8 +1046,8 @@ int launch_closed_n(K kern, int threads, const ClosedNArgs& a, hipStream_t s) {
 // levels -> the reconstruction of nh_intra_rdo_planes_closed_n.  Stage R
 // (k_dequant_inv_n, nh_decode_n.hip, earlier on the stream) has put every
 // block's residual into rec; this kernel is the dependent part, stage P.  The
-// schedule is the encoder's above: ClosedNArgs / closed_n_layout / closed_row /
-// poll_top / launch_closed_n as they are, rows claimed by ticket in
+// schedule is the encoder's above: ClosedNArgs / closed_row / poll_top /
+// launch_closed_n and, on the host, closed_n_begin as they are, rows claimed by ticket in
 // closed_ticket's order 1, tagged 64-bit line words, the bottom row published
 // before the block's recon stores, the top-left sample and the left column
 // carried along the row, the bounded poll, work[1] honoured by every waiter.
@@ -1229,6 +1223,134 @@ __global__ void __launch_bounds__(64) k_intra_dec_closed_n(ClosedNArgs a) {
     }
 }
 
+// ===========================================================================
+// Host side: one launch path per form -- open loop, closed-loop encoder -- and
+// one start for everything on the row wavefront, the decoder included.  RD picks
+// the kernels with the rate term, which serve N = 8 on
+// the N-lane chains too (4 blocks per workgroup in the open loop, 28 chains over
+// 2 rounds in the closed loop); without it N = 8 never gets here.
+// ===========================================================================
+template <class A>
+void set_qp(A& a, int qp, int N) {
+    int per, rem;
+    split_qp(qp, log2_of(N), &a.qp, &per, &rem);
+    a.dq_scale = dequant_scale(rem);
+    a.dq_per = per;
+}
+
+// The open loop, a launch per set that holds a block.  d_acc: the per-plane sums the kernels add to -- RD:
+// three words per plane (sum J, sum D, sum R); otherwise one (the SSE), or null for none.
+template <bool RD>
+int launch_rdo_n(const int16_t* d_src, const nh_plane_set* sets, int nsets, int N, int use_dst, int qp, int64_t lambda,
+                 uint8_t* d_modes, int32_t* d_lvl, int16_t* d_recon, int64_t* d_acc, hipStream_t s) {
+    RdoNArgs a{};
+    set_qp(a, qp, N);
+    a.lambda = (unsigned long long)lambda;
+    const int bpw = N == 4 ? kLaneSlots : 32 / N, threads = N == 4 ? 256 : 224;   // blocks per workgroup
+    int64_t moff = 0, soff = 0;
+    for (int k = 0; k < nsets; ++k) {
+        const nh_plane_set& S = sets[k];
+        const int64_t planes = (int64_t)S.planes_per_group * S.num_groups;
+        const int nblk = (S.width / N) * (S.height / N);
+        if (nblk && planes) {
+            a.src = d_src + S.base;
+            a.lvl = d_lvl + S.base;
+            a.recon = d_recon + S.base;
+            a.modes = d_modes + moff;
+            if constexpr (RD) a.stats = (unsigned long long*)(d_acc + kRdoStats * soff);
+            else a.sse = d_acc ? (unsigned long long*)(d_acc + soff) : nullptr;
+            a.w = S.width;
+            a.h = S.height;
+            a.pitch = S.pitch;
+            a.vec_out = !(S.pitch & 7) && !((S.base | S.plane_stride | S.group_stride) & 7) &&
+                        !((uintptr_t)d_lvl & 15) && !((uintptr_t)d_recon & 15);
+            a.group_stride = S.group_stride;
+            a.plane_stride = S.plane_stride;
+            a.ppg = S.planes_per_group;
+            const dim3 grid((unsigned)((nblk + bpw - 1) / bpw), (unsigned)planes);
+            if (N == 4 && use_dst) k_intra_rdo_n<4, true, RD><<<grid, threads, 0, s>>>(a);
+            else if (N == 4) k_intra_rdo_n<4, false, RD><<<grid, threads, 0, s>>>(a);
+            else if (N == 16) k_intra_rdo_n<16, false, RD><<<grid, threads, 0, s>>>(a);
+            else if (N == 32) k_intra_rdo_n<32, false, RD><<<grid, threads, 0, s>>>(a);
+            else if constexpr (RD) k_intra_rdo_n<8, false, true><<<grid, threads, 0, s>>>(a);
+            NH_HIP(hipGetLastError());
+        }
+        moff += planes * nblk;
+        soff += planes;
+    }
+    return NH_OK;
+}
+
+int64_t closed_n_work_bytes(const ClosedNArgs& a) { return 4ll * kClosedNLines0 + 8ll * a.lines_total; }
+
+// The *_workspace_bytes entry points: -1 with the refusal in nh_last_error.  at8: the 8x8 function that
+// N = 8 forwards to, or null where N = 8 runs on the line words of this file (the RD form).
+int64_t closed_n_workspace_bytes(const char* who, const nh_plane_set* sets, int nsets, int block_size,
+                                 int64_t (*at8)(const nh_plane_set*, int)) {
+    if (!sets) {
+        set_error(std::string(who) + ": null argument");
+        return -1;
+    }
+    if (check_rdo_n_args(who, sets, nsets, block_size, 0, 0)) return -1;
+    if (block_size == 8 && at8) return at8(sets, nsets);
+    ClosedNArgs a;
+    if (closed_n_layout(who, sets, nsets, block_size, a)) return -1;
+    return closed_n_work_bytes(a);
+}
+
+// How every call on the row wavefront starts; a.rec, a.work (and a.sse) are the caller's already.  First
+// the refusals, before any device call: the layout's, the workspace's and, elem_ok false, the decoder's own.
+// Then the workspace zeroed (ticket, status, line tags), zero_stats: the kRdoStats words per plane at a.sse
+// zeroed, vec_out dropped unless the caller's buffers are 16-B aligned (vec_ok), and every sample outside
+// full blocks set to 0.
+int closed_n_begin(const char* who, const nh_plane_set* sets, int nsets, int N, ClosedNArgs& a, hipStream_t s,
+                   bool vec_ok, bool zero_stats = false, bool elem_ok = true) {
+    NH_TRY(closed_n_layout(who, sets, nsets, N, a));
+    if ((uintptr_t)a.work & 7) {
+        set_error(std::string(who) + ": workspace must be 8-byte aligned");
+        return NH_EARG;
+    }
+    if (!elem_ok) {
+        set_error(std::string(who) + ": buffers must be aligned to their element size");
+        return NH_EARG;
+    }
+    NH_HIP(hipMemsetAsync(a.work, 0, (size_t)closed_n_work_bytes(a), s));
+    const int64_t planes = planes_of(sets, nsets);
+    if (zero_stats && planes) NH_HIP(hipMemsetAsync(a.sse, 0, 8ull * kRdoStats * (uint64_t)planes, s));
+    for (int k = 0; k < nsets; ++k) {
+        a.set[k].vec_out = a.set[k].vec_out && vec_ok;
+        if (a.set[k].np > 0 && (int64_t)a.set[k].w * a.set[k].h > 0)
+            k_zero_partial_n<<<dim3(64, (unsigned)a.set[k].np), 256, 0, s>>>(a.rec, a.set[k], N);
+    }
+    NH_HIP(hipGetLastError());
+    return NH_OK;
+}
+
+// The closed-loop encoder.  d_acc: the per-plane sums as launch_rdo_n's; RD zeroes them, without it the
+// kernels add to what the caller put there.
+template <bool RD>
+int launch_rdo_closed_n(const char* who, const int16_t* d_src, const nh_plane_set* sets, int nsets, int N, int use_dst,
+                        int qp, int64_t lambda, uint8_t* d_modes, int32_t* d_lvl, int16_t* d_recon, int64_t* d_acc,
+                        void* d_work, hipStream_t s) {
+    ClosedNArgs a{};
+    a.src = d_src;
+    a.lvl = d_lvl;
+    a.rec = d_recon;
+    a.modes = d_modes;
+    a.sse = (unsigned long long*)d_acc;
+    a.work = (int32_t*)d_work;
+    NH_TRY(closed_n_begin(who, sets, nsets, N, a, s, !((uintptr_t)d_lvl & 15) && !((uintptr_t)d_recon & 15), RD));
+    set_qp(a, qp, N);
+    a.lambda = (unsigned long long)lambda;
+    if (a.total_rows <= 0) return NH_OK;
+    if (N == 4 && use_dst) return launch_closed_n(k_intra_rdo_closed_lane<true, RD>, 64, a, s);
+    if (N == 4) return launch_closed_n(k_intra_rdo_closed_lane<false, RD>, 64, a, s);
+    if (N == 16) return launch_closed_n(k_intra_rdo_closed_tile<16, RD>, 224, a, s);
+    if (N == 32) return launch_closed_n(k_intra_rdo_closed_tile<32, RD>, 224, a, s);
+    if constexpr (RD) return launch_closed_n(k_intra_rdo_closed_tile<8, true>, 224, a, s);
+    return NH_OK;
+}
+
 }  // namespace
 }  // namespace nh
 
@@ -1243,58 +1365,37 @@ extern "C" int nh_intra_rdo_planes_n(const int16_t* d_src, const nh_plane_set* s
     }
     NH_TRY(check_rdo_n_args("nh_intra_rdo_planes_n", sets, nsets, block_size, use_dst, qp));
     if (block_size == 8) return nh_intra_rdo_planes(d_src, sets, nsets, qp, d_modes, d_lvl, d_recon, d_sse, stream);
+    return launch_rdo_n<false>(d_src, sets, nsets, block_size, use_dst, qp, 0, d_modes, d_lvl, d_recon, d_sse,
+                               as_stream(stream));
+}
 
-    const int N = block_size, log2n = N == 4 ? 2 : N == 16 ? 4 : 5;
-    RdoNArgs a{};
-    int per, rem;
-    split_qp(qp, log2n, &a.qp, &per, &rem);
-    a.dq_scale = dequant_scale(rem);
-    a.dq_per = per;
-    const hipStream_t s = as_stream(stream);
-    int64_t moff = 0, soff = 0;
-    for (int k = 0; k < nsets; ++k) {
-        const nh_plane_set& S = sets[k];
-        const int64_t planes = (int64_t)S.planes_per_group * S.num_groups;
-        const int nblk = (S.width / N) * (S.height / N);
-        if (nblk && planes) {
-            a.src = d_src + S.base;
-            a.lvl = d_lvl + S.base;
-            a.recon = d_recon + S.base;
-            a.modes = d_modes + moff;
-            a.sse = d_sse ? (unsigned long long*)(d_sse + soff) : nullptr;
-            a.w = S.width;
-            a.h = S.height;
-            a.pitch = S.pitch;
-            a.vec_out = !(S.pitch & 7) && !((S.base | S.plane_stride | S.group_stride) & 7) &&
-                        !((uintptr_t)d_lvl & 15) && !((uintptr_t)d_recon & 15);
-            a.group_stride = S.group_stride;
-            a.plane_stride = S.plane_stride;
-            a.ppg = S.planes_per_group;
-            const unsigned py = (unsigned)planes;
-            if (N == 4) {
-                const dim3 grid((unsigned)((nblk + kLaneSlots - 1) / kLaneSlots), py);
-                if (use_dst) k_intra_rdo_n<4, true><<<grid, 256, 0, s>>>(a);
-                else k_intra_rdo_n<4, false><<<grid, 256, 0, s>>>(a);
-            } else if (N == 16) {
-                k_intra_rdo_n<16, false><<<dim3((unsigned)((nblk + 1) / 2), py), 224, 0, s>>>(a);
-            } else {
-                k_intra_rdo_n<32, false><<<dim3((unsigned)nblk, py), 224, 0, s>>>(a);
-            }
-            NH_HIP(hipGetLastError());
-        }
-        moff += planes * nblk;
-        soff += planes;
+extern "C" int nh_intra_rdo_rd_planes_n(const int16_t* d_src, const nh_plane_set* sets, int nsets, int block_size,
+                                        int use_dst, int qp, int64_t lambda, uint8_t* d_modes, int32_t* d_lvl,
+                                        int16_t* d_recon, int64_t* d_stats, void* stream) {
+    if (!d_src || !sets || !d_modes || !d_lvl || !d_recon || !d_stats) {
+        set_error("nh_intra_rdo_rd_planes_n: null argument");
+        return NH_EARG;
     }
-    return NH_OK;
+    NH_TRY(check_rd_args("nh_intra_rdo_rd_planes_n", sets, nsets, block_size, use_dst, qp, lambda, d_stats));
+    const int64_t planes = planes_of(sets, nsets);
+    if (!planes) return NH_OK;   // nothing to code, no stats word to zero
+    const hipStream_t s = as_stream(stream);
+    NH_HIP(hipMemsetAsync(d_stats, 0, 8ull * kRdoStats * (uint64_t)planes, s));
+    return launch_rdo_n<true>(d_src, sets, nsets, block_size, use_dst, qp, lambda, d_modes, d_lvl, d_recon, d_stats, s);
 }
 
 extern "C" int64_t nh_intra_rdo_closed_n_workspace_bytes(const nh_plane_set* sets, int nsets, int block_size) {
-    if (!sets) return -1;
-    if (check_rdo_n_args("nh_intra_rdo_closed_n_workspace_bytes", sets, nsets, block_size, 0, 0)) return -1;
-    if (block_size == 8) return nh_intra_rdo_closed_workspace_bytes(sets, nsets);
-    ClosedNArgs a;
-    if (closed_n_layout(sets, nsets, block_size, a)) return -1;
-    return 4ll * kClosedNLines0 + 8ll * a.lines_total;
+    return closed_n_workspace_bytes("nh_intra_rdo_closed_n_workspace_bytes", sets, nsets, block_size,
+                                    nh_intra_rdo_closed_workspace_bytes);
+}
+
+extern "C" int64_t nh_intra_rdo_rd_closed_n_workspace_bytes(const nh_plane_set* sets, int nsets, int block_size) {
+    return closed_n_workspace_bytes("nh_intra_rdo_rd_closed_n_workspace_bytes", sets, nsets, block_size, nullptr);
+}
+
+extern "C" int64_t nh_intra_decode_closed_n_workspace_bytes(const nh_plane_set* sets, int nsets, int block_size) {
+    return closed_n_workspace_bytes("nh_intra_decode_closed_n_workspace_bytes", sets, nsets, block_size,
+                                    nh_intra_decode_closed_workspace_bytes);
 }
 
 extern "C" int nh_intra_rdo_planes_closed_n(const int16_t* d_src, const nh_plane_set* sets, int nsets, int block_size,
@@ -1307,55 +1408,21 @@ extern "C" int nh_intra_rdo_planes_closed_n(const int16_t* d_src, const nh_plane
     NH_TRY(check_rdo_n_args("nh_intra_rdo_planes_closed_n", sets, nsets, block_size, use_dst, qp));
     if (block_size == 8)
         return nh_intra_rdo_planes_closed(d_src, sets, nsets, qp, d_modes, d_lvl, d_recon, d_sse, d_work, stream);
-    const int N = block_size, log2n = N == 4 ? 2 : N == 16 ? 4 : 5;
-    ClosedNArgs a{};
-    if (closed_n_layout(sets, nsets, N, a)) {
-        set_error("nh_intra_rdo_planes_closed_n: bad plane set (sizes <= 65535, < 2^30 block rows)");
-        return NH_EARG;
-    }
-    if ((uintptr_t)d_work & 7) {
-        set_error("nh_intra_rdo_planes_closed_n: workspace must be 8-byte aligned");
-        return NH_EARG;
-    }
-    int per, rem;
-    split_qp(qp, log2n, &a.qp, &per, &rem);
-    a.dq_scale = dequant_scale(rem);
-    a.dq_per = per;
-    a.src = d_src;
-    a.lvl = d_lvl;
-    a.rec = d_recon;
-    a.modes = d_modes;
-    a.sse = (unsigned long long*)d_sse;
-    a.work = (int32_t*)d_work;
-    const bool aligned = !((uintptr_t)d_lvl & 15) && !((uintptr_t)d_recon & 15);
-    const hipStream_t s = as_stream(stream);
-    NH_HIP(hipMemsetAsync(d_work, 0, 4ull * kClosedNLines0 + 8ull * a.lines_total, s));
-    for (int k = 0; k < nsets; ++k) {
-        a.set[k].vec_out = a.set[k].vec_out && aligned;
-        if (a.set[k].np > 0 && (int64_t)a.set[k].w * a.set[k].h > 0)
-            k_zero_partial_n<<<dim3(64, (unsigned)a.set[k].np), 256, 0, s>>>(d_recon, a.set[k], N);
-    }
-    NH_HIP(hipGetLastError());
-    if (a.total_rows > 0) {
-        if (N == 4) {
-            if (use_dst) NH_TRY(launch_closed_n(k_intra_rdo_closed_lane<true>, 64, a, s));
-            else NH_TRY(launch_closed_n(k_intra_rdo_closed_lane<false>, 64, a, s));
-        } else if (N == 16) {
-            NH_TRY(launch_closed_n(k_intra_rdo_closed_tile<16>, 224, a, s));
-        } else {
-            NH_TRY(launch_closed_n(k_intra_rdo_closed_tile<32>, 224, a, s));
-        }
-    }
-    return NH_OK;
+    return launch_rdo_closed_n<false>("nh_intra_rdo_planes_closed_n", d_src, sets, nsets, block_size, use_dst, qp, 0,
+                                      d_modes, d_lvl, d_recon, d_sse, d_work, as_stream(stream));
 }
 
-extern "C" int64_t nh_intra_decode_closed_n_workspace_bytes(const nh_plane_set* sets, int nsets, int block_size) {
-    if (!sets) return -1;
-    if (check_decode_n_args("nh_intra_decode_closed_n_workspace_bytes", sets, nsets, block_size, 0)) return -1;
-    if (block_size == 8) return nh_intra_decode_closed_workspace_bytes(sets, nsets);
-    ClosedNArgs a;
-    if (closed_n_layout(sets, nsets, block_size, a)) return -1;
-    return 4ll * kClosedNLines0 + 8ll * a.lines_total;
+extern "C" int nh_intra_rdo_rd_planes_closed_n(const int16_t* d_src, const nh_plane_set* sets, int nsets,
+                                               int block_size, int use_dst, int qp, int64_t lambda, uint8_t* d_modes,
+                                               int32_t* d_lvl, int16_t* d_recon, int64_t* d_stats, void* d_work,
+                                               void* stream) {
+    if (!d_src || !sets || !d_modes || !d_lvl || !d_recon || !d_stats || !d_work) {
+        set_error("nh_intra_rdo_rd_planes_closed_n: null argument");
+        return NH_EARG;
+    }
+    NH_TRY(check_rd_args("nh_intra_rdo_rd_planes_closed_n", sets, nsets, block_size, use_dst, qp, lambda, d_stats));
+    return launch_rdo_closed_n<true>("nh_intra_rdo_rd_planes_closed_n", d_src, sets, nsets, block_size, use_dst, qp,
+                                     lambda, d_modes, d_lvl, d_recon, d_stats, d_work, as_stream(stream));
 }
 
 extern "C" int nh_intra_decode_planes_closed_n(const uint8_t* d_modes, const int32_t* d_lvl, const nh_plane_set* sets,
@@ -1365,35 +1432,17 @@ extern "C" int nh_intra_decode_planes_closed_n(const uint8_t* d_modes, const int
         set_error("nh_intra_decode_planes_closed_n: null argument");
         return NH_EARG;
     }
-    NH_TRY(check_decode_n_args("nh_intra_decode_planes_closed_n", sets, nsets, block_size, use_dst));
+    NH_TRY(check_rdo_n_args("nh_intra_decode_planes_closed_n", sets, nsets, block_size, use_dst, qp, false));
     if (block_size == 8) return nh_intra_decode_planes_closed(d_modes, d_lvl, sets, nsets, qp, d_recon, d_work, stream);
     const int N = block_size;
     ClosedNArgs a{};
-    if (closed_n_layout(sets, nsets, N, a)) {
-        set_error("nh_intra_decode_planes_closed_n: bad plane set (sizes <= 65535, < 2^30 block rows)");
-        return NH_EARG;
-    }
-    if ((uintptr_t)d_work & 7) {
-        set_error("nh_intra_decode_planes_closed_n: workspace must be 8-byte aligned");
-        return NH_EARG;
-    }
-    if (((uintptr_t)d_lvl & 3) || ((uintptr_t)d_recon & 1)) {
-        set_error("nh_intra_decode_planes_closed_n: buffers must be aligned to their element size");
-        return NH_EARG;
-    }
     a.lvl = const_cast<int32_t*>(d_lvl);     // read only, by stage R (the encoder's argument block)
     a.rec = d_recon;
     a.modes = const_cast<uint8_t*>(d_modes);   // read only
     a.work = (int32_t*)d_work;
-    const bool aligned = !((uintptr_t)d_recon & 15);
     const hipStream_t s = as_stream(stream);
-    NH_HIP(hipMemsetAsync(d_work, 0, 4ull * kClosedNLines0 + 8ull * a.lines_total, s));
-    for (int k = 0; k < nsets; ++k) {
-        a.set[k].vec_out = a.set[k].vec_out && aligned;
-        if (a.set[k].np > 0 && (int64_t)a.set[k].w * a.set[k].h > 0)
-            k_zero_partial_n<<<dim3(64, (unsigned)a.set[k].np), 256, 0, s>>>(d_recon, a.set[k], N);
-    }
-    NH_HIP(hipGetLastError());
+    NH_TRY(closed_n_begin("nh_intra_decode_planes_closed_n", sets, nsets, N, a, s, !((uintptr_t)d_recon & 15), false,
+                          !((uintptr_t)d_lvl & 3) && !((uintptr_t)d_recon & 1)));
     // stage R: every block's residual into d_recon (the wavefront reads neighbours only from line words, LDS
     // and registers, so a block's residual is read from, and its recon written to, the same place)
     NH_TRY(nh_dequant_inv_planes_n(d_lvl, 4, d_recon, sets, nsets, N, use_dst, qp, stream));
@@ -1411,166 +1460,3 @@ extern "C" int nh_intra_decode_planes_closed_n(const uint8_t* d_modes, const int
     return NH_OK;
 }
 
-// ===========================================================================
-// The RD forms: the kernels above with RD = true, at
-// N = 4, 8, 16 and 32 -- N = 8 on the N-lane chains too (4 blocks per workgroup
-// in the open loop, 28 chains over 2 rounds in the closed loop).
-// ===========================================================================
-namespace nh {
-namespace {
-
-// The refusals the two RD entry points add to check_rdo_n_args'.
-int check_rd_args(const char* who, const nh_plane_set* sets, int nsets, int block_size, int use_dst, int qp,
-                  int64_t lambda, const void* d_stats) {
-    NH_TRY(check_rdo_n_args(who, sets, nsets, block_size, use_dst, qp));
-    if (lambda < 0 || lambda > 0x7fffffffll) {
-        set_error(std::string(who) + ": lambda outside 0..2^31-1");
-        return NH_EARG;
-    }
-    if ((uintptr_t)d_stats & 7) {
-        set_error(std::string(who) + ": d_stats must be 8-byte aligned");
-        return NH_EARG;
-    }
-    return NH_OK;
-}
-
-int64_t planes_of(const nh_plane_set* sets, int nsets) {
-    int64_t n = 0;
-    for (int k = 0; k < nsets; ++k) n += (int64_t)sets[k].planes_per_group * sets[k].num_groups;
-    return n;
-}
-
-int log2_of(int n) { return n == 4 ? 2 : n == 8 ? 3 : n == 16 ? 4 : 5; }
-
-}  // namespace
-}  // namespace nh
-
-extern "C" int nh_intra_rdo_rd_planes_n(const int16_t* d_src, const nh_plane_set* sets, int nsets, int block_size,
-                                        int use_dst, int qp, int64_t lambda, uint8_t* d_modes, int32_t* d_lvl,
-                                        int16_t* d_recon, int64_t* d_stats, void* stream) {
-    if (!d_src || !sets || !d_modes || !d_lvl || !d_recon || !d_stats) {
-        set_error("nh_intra_rdo_rd_planes_n: null argument");
-        return NH_EARG;
-    }
-    NH_TRY(check_rd_args("nh_intra_rdo_rd_planes_n", sets, nsets, block_size, use_dst, qp, lambda, d_stats));
-    const int64_t total_planes = planes_of(sets, nsets);
-    if (!total_planes) return NH_OK;   // nothing to code, no stats word to zero
-
-    const int N = block_size;
-    RdoNArgs a{};
-    int per, rem;
-    split_qp(qp, log2_of(N), &a.qp, &per, &rem);
-    a.dq_scale = dequant_scale(rem);
-    a.dq_per = per;
-    a.lambda = (unsigned long long)lambda;
-    const hipStream_t s = as_stream(stream);
-    NH_HIP(hipMemsetAsync(d_stats, 0, 8ull * kRdoStats * (uint64_t)total_planes, s));
-    int64_t moff = 0, soff = 0;
-    for (int k = 0; k < nsets; ++k) {
-        const nh_plane_set& S = sets[k];
-        const int64_t planes = (int64_t)S.planes_per_group * S.num_groups;
-        const int nblk = (S.width / N) * (S.height / N);
-        if (nblk && planes) {
-            a.src = d_src + S.base;
-            a.lvl = d_lvl + S.base;
-            a.recon = d_recon + S.base;
-            a.modes = d_modes + moff;
-            a.sse = nullptr;
-            a.stats = (unsigned long long*)(d_stats + kRdoStats * soff);
-            a.w = S.width;
-            a.h = S.height;
-            a.pitch = S.pitch;
-            a.vec_out = !(S.pitch & 7) && !((S.base | S.plane_stride | S.group_stride) & 7) &&
-                        !((uintptr_t)d_lvl & 15) && !((uintptr_t)d_recon & 15);
-            a.group_stride = S.group_stride;
-            a.plane_stride = S.plane_stride;
-            a.ppg = S.planes_per_group;
-            const unsigned py = (unsigned)planes;
-            if (N == 4) {
-                const dim3 grid((unsigned)((nblk + kLaneSlots - 1) / kLaneSlots), py);
-                if (use_dst) k_intra_rdo_n<4, true, true><<<grid, 256, 0, s>>>(a);
-                else k_intra_rdo_n<4, false, true><<<grid, 256, 0, s>>>(a);
-            } else if (N == 8) {
-                k_intra_rdo_n<8, false, true><<<dim3((unsigned)((nblk + 3) / 4), py), 224, 0, s>>>(a);
-            } else if (N == 16) {
-                k_intra_rdo_n<16, false, true><<<dim3((unsigned)((nblk + 1) / 2), py), 224, 0, s>>>(a);
-            } else {
-                k_intra_rdo_n<32, false, true><<<dim3((unsigned)nblk, py), 224, 0, s>>>(a);
-            }
-            NH_HIP(hipGetLastError());
-        }
-        moff += planes * nblk;
-        soff += planes;
-    }
-    return NH_OK;
-}
-
-extern "C" int64_t nh_intra_rdo_rd_closed_n_workspace_bytes(const nh_plane_set* sets, int nsets, int block_size) {
-    if (!sets) {
-        set_error("nh_intra_rdo_rd_closed_n_workspace_bytes: null argument");
-        return -1;
-    }
-    if (check_rdo_n_args("nh_intra_rdo_rd_closed_n_workspace_bytes", sets, nsets, block_size, 0, 0)) return -1;
-    ClosedNArgs a;
-    if (closed_n_layout(sets, nsets, block_size, a)) {
-        set_error("nh_intra_rdo_rd_closed_n_workspace_bytes: bad plane set (sizes <= 65535, < 2^30 block rows)");
-        return -1;
-    }
-    return 4ll * kClosedNLines0 + 8ll * a.lines_total;
-}
-
-extern "C" int nh_intra_rdo_rd_planes_closed_n(const int16_t* d_src, const nh_plane_set* sets, int nsets,
-                                               int block_size, int use_dst, int qp, int64_t lambda, uint8_t* d_modes,
-                                               int32_t* d_lvl, int16_t* d_recon, int64_t* d_stats, void* d_work,
-                                               void* stream) {
-    if (!d_src || !sets || !d_modes || !d_lvl || !d_recon || !d_stats || !d_work) {
-        set_error("nh_intra_rdo_rd_planes_closed_n: null argument");
-        return NH_EARG;
-    }
-    NH_TRY(check_rd_args("nh_intra_rdo_rd_planes_closed_n", sets, nsets, block_size, use_dst, qp, lambda, d_stats));
-    const int N = block_size;
-    ClosedNArgs a{};
-    if (closed_n_layout(sets, nsets, N, a)) {
-        set_error("nh_intra_rdo_rd_planes_closed_n: bad plane set (sizes <= 65535, < 2^30 block rows)");
-        return NH_EARG;
-    }
-    if ((uintptr_t)d_work & 7) {
-        set_error("nh_intra_rdo_rd_planes_closed_n: workspace must be 8-byte aligned");
-        return NH_EARG;
-    }
-    int per, rem;
-    split_qp(qp, log2_of(N), &a.qp, &per, &rem);
-    a.dq_scale = dequant_scale(rem);
-    a.dq_per = per;
-    a.lambda = (unsigned long long)lambda;
-    a.src = d_src;
-    a.lvl = d_lvl;
-    a.rec = d_recon;
-    a.modes = d_modes;
-    a.sse = (unsigned long long*)d_stats;   // three words per plane in the RD kernels
-    a.work = (int32_t*)d_work;
-    const bool aligned = !((uintptr_t)d_lvl & 15) && !((uintptr_t)d_recon & 15);
-    const hipStream_t s = as_stream(stream);
-    NH_HIP(hipMemsetAsync(d_work, 0, 4ull * kClosedNLines0 + 8ull * a.lines_total, s));
-    const int64_t total_planes = planes_of(sets, nsets);
-    if (total_planes) NH_HIP(hipMemsetAsync(d_stats, 0, 8ull * kRdoStats * (uint64_t)total_planes, s));
-    for (int k = 0; k < nsets; ++k) {
-        a.set[k].vec_out = a.set[k].vec_out && aligned;
-        if (a.set[k].np > 0 && (int64_t)a.set[k].w * a.set[k].h > 0)
-            k_zero_partial_n<<<dim3(64, (unsigned)a.set[k].np), 256, 0, s>>>(d_recon, a.set[k], N);
-    }
-    NH_HIP(hipGetLastError());
-    if (a.total_rows > 0) {
-        if (N == 4) {
-            if (use_dst) NH_TRY(launch_closed_n(k_intra_rdo_closed_lane<true, true>, 64, a, s));
-            else NH_TRY(launch_closed_n(k_intra_rdo_closed_lane<false, true>, 64, a, s));
-        } else if (N == 8) {
-            NH_TRY(launch_closed_n(k_intra_rdo_closed_tile<8, true>, 224, a, s));
-        } else if (N == 16) {
-            NH_TRY(launch_closed_n(k_intra_rdo_closed_tile<16, true>, 224, a, s));
-        } else {
-            NH_TRY(launch_closed_n(k_intra_rdo_closed_tile<32, true>, 224, a, s));
-        }
-    }
-    return NH_OK;
-}

@@ -130,8 +130,19 @@ def yuv420_plane_sets(num_frames: int, width: int, height: int, frame_stride: in
             plane_set(base + ys, cw, ch, cw, 2, num_frames, cw * ch, fs)]
 
 
+def _set_array(sets: Sequence[PlaneSet]):
+    """``sets`` as the C array the library takes (an empty list still gets an address)."""
+    return (PlaneSet * max(1, len(sets)))(*sets)
+
+
+def _set_counts(sets: Sequence[PlaneSet], n: int):
+    """(full n x n blocks, planes) over every plane of ``sets``."""
+    planes = [s.planes_per_group * s.num_groups for s in sets]
+    return sum((s.width // n) * (s.height // n) * p for s, p in zip(sets, planes)), sum(planes)
+
+
 def blocks_in(sets: Sequence[PlaneSet]) -> int:
-    return sum((s.width // 8) * (s.height // 8) * s.planes_per_group * s.num_groups for s in sets)
+    return _set_counts(sets, 8)[0]
 
 
 DEFAULT_VARIANT = 4341   # nontemporal loads+stores, >= 5 waves/SIMD, XCD-aware order (see nh_fused8x8.hip)
@@ -180,7 +191,7 @@ def fwd8x8_quant(res, sets: Sequence[PlaneSet], qp: int = 32, is_intra: bool = T
         out = torch.zeros_like(res)
     _need(out, torch.int16, "fwd8x8_quant(out)")
     sets_fit(sets, min(res.numel(), out.numel()), "fwd8x8_quant")
-    arr = (PlaneSet * len(sets))(*sets)
+    arr = _set_array(sets)
     L = _lib.load() if int(variant) in PRODUCT_VARIANTS else _lib.load_ab()   # the A/B forms live in the A/B build
     check(L.nh_fwd8x8_quant_planes_variant(res.data_ptr(), out.data_ptr(), arr, len(sets), int(qp),
                                            int(bool(is_intra)), int(variant), C.c_void_p(_stream(stream, res.device))),
@@ -204,7 +215,7 @@ def fwd8x8_quant_ex(res, sets: Sequence[PlaneSet], qp: int = 32, is_intra: bool 
     nb = blocks_in(sets)
     t_nnz = torch.empty(nb, dtype=torch.uint8, device=res.device) if nnz else None
     t_bits = torch.empty(nb, dtype=torch.int32, device=res.device) if bits else None
-    arr = (PlaneSet * len(sets))(*sets)
+    arr = _set_array(sets)
     check(_lib.load().nh_fwd8x8_quant_planes_ex(
         res.data_ptr(), out.data_ptr(), arr, len(sets), int(qp), int(bool(is_intra)),
         t_nnz.data_ptr() if nnz else None, t_bits.data_ptr() if bits else None, C.c_void_p(_stream(stream, res.device))))
@@ -279,32 +290,76 @@ def intra_rdo_plane(src, qp: int = 32, pitch: int | None = None, stream=None):
     return modes, lvl, rec, sse
 
 
+def _rdo_prepare(what: str, src, sets: Sequence[PlaneSet], block_size: int, lvl, rec, stats: bool = False):
+    """Argument checks and default outputs of the config-3 encoders; returns (n, lvl, rec,
+    modes, acc, nmodes, nplanes).  ``acc`` holds the per-plane sums: sse int64 (planes,),
+    zeroed for the kernels to add to, or with ``stats`` (the RD forms, DESIGN.md §3.3b,
+    §3.7b) int64 (planes, 3), overwritten by the call."""
+    torch = _torch()
+    _need(src, torch.int16, f"{what}(src)")
+    n = int(block_size)
+    if n not in (4, 8, 16, 32):
+        raise ValueError(f"{what}: block_size must be 4, 8, 16 or 32, got {block_size}")
+    sets_fit(sets, src.numel(), what)
+    nmodes, nplanes = _set_counts(sets, n)
+    dev = src.device
+    if lvl is None:
+        lvl = torch.zeros(src.shape, dtype=torch.int32, device=dev)
+    if rec is None:
+        rec = torch.zeros(src.shape, dtype=torch.int16, device=dev)
+    _need(lvl, torch.int32, f"{what}(lvl)")
+    _need(rec, torch.int16, f"{what}(rec)")
+    if lvl.numel() < src.numel() or rec.numel() < src.numel():
+        raise ValueError(f"{what}: lvl / rec smaller than src")
+    modes = torch.zeros(max(1, nmodes), dtype=torch.uint8, device=dev)
+    if stats:
+        acc = torch.empty((max(1, nplanes), 3), dtype=torch.int64, device=dev)
+    else:
+        acc = torch.zeros(max(1, nplanes), dtype=torch.int64, device=dev)
+    return n, lvl, rec, modes, acc, nmodes, nplanes
+
+
+def _rdo_rd_prepare(what: str, src, sets: Sequence[PlaneSet], block_size: int, lam: int, lvl, rec):
+    if not 0 <= int(lam) <= 2 ** 31 - 1:
+        raise ValueError(f"{what}: lam (lambda) must be in 0..2^31-1")
+    return _rdo_prepare(what, src, sets, block_size, lvl, rec, stats=True)
+
+
+def _closed_status(work, st: int, what: str, status2: str | None = None):
+    """Read the status word of a closed-loop call's workspace on stream ``st`` (a host round
+    trip): 0 returns; 2 raises ValueError with ``status2`` where the call has such a
+    refusal (a bad map); anything else is a stalled wavefront, RuntimeError."""
+    status = C.c_int(0)
+    check(_lib.load().nh_intra_rdo_closed_status(work.data_ptr(), C.byref(status), C.c_void_p(st)))
+    if status.value == 2 and status2:
+        raise ValueError(f"{what}: {status2}")
+    if status.value:
+        raise RuntimeError("%s: the device wavefront stalled (status %d)" % (what, status.value))
+
+
+def _closed_call(what: str, wb: int, dev, stream, call, status2: str | None = None):
+    """The end of a closed-loop config-3 call.  ``wb``: the library's workspace size for
+    it, negative for a refusal (ValueError with the library's text); ``call(work, st)``
+    makes the library call on a fresh workspace; then the status word is checked."""
+    if wb < 0:
+        raise ValueError(f"{what}: bad plane sets or argument: " + _lib.load().nh_last_error().decode(errors="replace"))
+    work = _torch().empty(max(2, (wb + 7) // 8 * 2), dtype=_torch().int32, device=dev)
+    st = _stream(stream, dev)
+    check(call(work.data_ptr(), C.c_void_p(st)), what)
+    _closed_status(work, st, what, status2)
+
+
 def intra_rdo_planes(src, sets: Sequence[PlaneSet], qp: int = 32, lvl=None, rec=None, stream=None):
     """Config 3 over every plane of ``sets`` -- a frame stream
     in one launch pair per set instead of a launch per plane.  Returns (modes
     uint8 [sum of per-plane (h/8)*(w/8), set order], lvl int32, recon int16
     (source layout), sse int64 per plane); the same results as ``intra_rdo_plane``
     plane by plane."""
-    torch = _torch()
-    _need(src, torch.int16, "intra_rdo_planes(src)")
-    sets_fit(sets, src.numel(), "intra_rdo_planes")
-    nmodes = sum((s.width // 8) * (s.height // 8) * s.planes_per_group * s.num_groups for s in sets)
-    nplanes = sum(s.planes_per_group * s.num_groups for s in sets)
-    dev = src.device
-    if lvl is None:
-        lvl = torch.zeros(src.shape, dtype=torch.int32, device=dev)
-    if rec is None:
-        rec = torch.zeros(src.shape, dtype=torch.int16, device=dev)
-    _need(lvl, torch.int32, "intra_rdo_planes(lvl)")
-    _need(rec, torch.int16, "intra_rdo_planes(rec)")
-    if lvl.numel() < src.numel() or rec.numel() < src.numel():
-        raise ValueError("intra_rdo_planes: lvl / rec smaller than src")
-    modes = torch.zeros(max(1, nmodes), dtype=torch.uint8, device=dev)
-    sse = torch.zeros(max(1, nplanes), dtype=torch.int64, device=dev)
-    arr = (PlaneSet * len(sets))(*sets)
-    check(_lib.load().nh_intra_rdo_planes(src.data_ptr(), arr, len(sets), int(qp), modes.data_ptr(), lvl.data_ptr(),
-                                          rec.data_ptr(), sse.data_ptr(), C.c_void_p(_stream(stream, dev))),
-          "intra_rdo_planes")
+    what = "intra_rdo_planes"
+    _, lvl, rec, modes, sse, nmodes, nplanes = _rdo_prepare(what, src, sets, 8, lvl, rec)
+    check(_lib.load().nh_intra_rdo_planes(src.data_ptr(), _set_array(sets), len(sets), int(qp), modes.data_ptr(),
+                                          lvl.data_ptr(), rec.data_ptr(), sse.data_ptr(),
+                                          C.c_void_p(_stream(stream, src.device))), what)
     return modes[:nmodes], lvl, rec, sse[:nplanes]
 
 
@@ -317,30 +372,32 @@ def intra_rdo_planes_n(src, sets: Sequence[PlaneSet], block_size: int, qp: int =
     (source layout; samples outside full blocks keep the caller's contents), sse
     int64 per plane).  A QP outside 0..51 raises ValueError (it is not clamped);
     N = 8 runs the ``intra_rdo_planes`` kernels."""
-    torch = _torch()
-    _need(src, torch.int16, "intra_rdo_planes_n(src)")
-    n = int(block_size)
-    if n not in (4, 8, 16, 32):
-        raise ValueError(f"intra_rdo_planes_n: block_size must be 4, 8, 16 or 32, got {block_size}")
-    sets_fit(sets, src.numel(), "intra_rdo_planes_n")
-    nmodes = sum((s.width // n) * (s.height // n) * s.planes_per_group * s.num_groups for s in sets)
-    nplanes = sum(s.planes_per_group * s.num_groups for s in sets)
-    dev = src.device
-    if lvl is None:
-        lvl = torch.zeros(src.shape, dtype=torch.int32, device=dev)
-    if rec is None:
-        rec = torch.zeros(src.shape, dtype=torch.int16, device=dev)
-    _need(lvl, torch.int32, "intra_rdo_planes_n(lvl)")
-    _need(rec, torch.int16, "intra_rdo_planes_n(rec)")
-    if lvl.numel() < src.numel() or rec.numel() < src.numel():
-        raise ValueError("intra_rdo_planes_n: lvl / rec smaller than src")
-    modes = torch.zeros(max(1, nmodes), dtype=torch.uint8, device=dev)
-    sse = torch.zeros(max(1, nplanes), dtype=torch.int64, device=dev)
-    arr = (PlaneSet * max(1, len(sets)))(*sets)
-    check(_lib.load().nh_intra_rdo_planes_n(src.data_ptr(), arr, len(sets), n, int(bool(use_dst)), int(qp),
+    what = "intra_rdo_planes_n"
+    n, lvl, rec, modes, sse, nmodes, nplanes = _rdo_prepare(what, src, sets, block_size, lvl, rec)
+    check(_lib.load().nh_intra_rdo_planes_n(src.data_ptr(), _set_array(sets), len(sets), n, int(bool(use_dst)), int(qp),
                                             modes.data_ptr(), lvl.data_ptr(), rec.data_ptr(), sse.data_ptr(),
-                                            C.c_void_p(_stream(stream, dev))), "intra_rdo_planes_n")
+                                            C.c_void_p(_stream(stream, src.device))), what)
     return modes[:nmodes], lvl, rec, sse[:nplanes]
+
+
+def _rdo_one_plane(what: str, planes_fn, src, block_size: int, pitch, *args, stream=None):
+    """``planes_fn(buffer, sets, block_size, *args)`` -- ``intra_rdo_planes_n`` or its RD
+    form -- on one int16 plane (H, W) whose rows are ``pitch`` (default W) samples apart."""
+    torch = _torch()
+    _need(src, torch.int16, what)
+    h, w = src.shape
+    p = int(pitch or w)
+    if p < w:
+        raise ValueError(f"{what}: pitch < width")
+    buf = src
+    if p != w:   # rows of the (H, W) tensor re-spaced: run on a pitched copy, return (H, W) views
+        buf = torch.zeros((h, p), dtype=torch.int16, device=src.device)
+        buf[:, :w] = src
+    modes, lvl, rec, acc = planes_fn(buf, [plane_set(0, w, h, p)], block_size, *args, stream=stream)
+    if p != w:
+        lvl, rec = lvl[:, :w], rec[:, :w]
+    n = int(block_size)
+    return modes.reshape(h // n, w // n), lvl, rec, acc
 
 
 def intra_rdo_plane_n(src, block_size: int, qp: int = 32, use_dst: bool = False, pitch: int | None = None,
@@ -348,21 +405,7 @@ def intra_rdo_plane_n(src, block_size: int, qp: int = 32, use_dst: bool = False,
     """``intra_rdo_planes_n`` on one int16 plane (H, W) whose rows are ``pitch`` (default
     W) samples apart: (modes u8 (H/N, W/N), levels int32 (H, W), recon int16 (H, W),
     sse int64 (1,))."""
-    torch = _torch()
-    _need(src, torch.int16, "intra_rdo_plane_n")
-    h, w = src.shape
-    p = int(pitch or w)
-    if p != w:   # rows of the (H, W) tensor re-spaced: run on a pitched copy, return (H, W) views
-        if p < w:
-            raise ValueError("intra_rdo_plane_n: pitch < width")
-        buf = torch.zeros((h, p), dtype=torch.int16, device=src.device)
-        buf[:, :w] = src
-        modes, lvl, rec, sse = intra_rdo_planes_n(buf, [plane_set(0, w, h, p)], block_size, qp, use_dst, stream=stream)
-        lvl, rec = lvl[:, :w], rec[:, :w]
-    else:
-        modes, lvl, rec, sse = intra_rdo_planes_n(src, [plane_set(0, w, h, w)], block_size, qp, use_dst, stream=stream)
-    n = int(block_size)
-    return modes.reshape(h // n, w // n), lvl, rec, sse
+    return _rdo_one_plane("intra_rdo_plane_n", intra_rdo_planes_n, src, block_size, pitch, qp, use_dst, stream=stream)
 
 
 def intra_rdo_closed(src, sets: Sequence[PlaneSet], qp: int = 32, lvl=None, rec=None, stream=None):
@@ -374,34 +417,13 @@ def intra_rdo_closed(src, sets: Sequence[PlaneSet], qp: int = 32, lvl=None, rec=
     the call (all sets) is in [0, 255]; one sample outside sends the whole call
     to the 32-bit form (same results, ~1.4x the time).  Split
     such streams into separate calls to keep the 8-bit ones fast."""
-    torch = _torch()
-    _need(src, torch.int16, "intra_rdo_closed(src)")
-    sets_fit(sets, src.numel(), "intra_rdo_closed")
+    what = "intra_rdo_closed"
+    _, lvl, rec, modes, sse, nmodes, nplanes = _rdo_prepare(what, src, sets, 8, lvl, rec)
     L = _lib.load()
-    arr = (PlaneSet * len(sets))(*sets)
-    wb = int(L.nh_intra_rdo_closed_workspace_bytes(arr, len(sets)))
-    if wb < 0:
-        raise ValueError("intra_rdo_closed: bad plane sets")
-    nmodes = sum((s.width // 8) * (s.height // 8) * s.planes_per_group * s.num_groups for s in sets)
-    nplanes = sum(s.planes_per_group * s.num_groups for s in sets)
-    if lvl is None:
-        lvl = torch.zeros(src.shape, dtype=torch.int32, device=src.device)
-    if rec is None:
-        rec = torch.zeros(src.shape, dtype=torch.int16, device=src.device)
-    _need(lvl, torch.int32, "intra_rdo_closed(lvl)")
-    _need(rec, torch.int16, "intra_rdo_closed(rec)")
-    if lvl.numel() < src.numel() or rec.numel() < src.numel():
-        raise ValueError("intra_rdo_closed: lvl / rec smaller than src")
-    modes = torch.zeros(max(1, nmodes), dtype=torch.uint8, device=src.device)
-    sse = torch.zeros(max(1, nplanes), dtype=torch.int64, device=src.device)
-    work = torch.empty((wb + 3) // 4, dtype=torch.int32, device=src.device)
-    st = C.c_void_p(_stream(stream, src.device))
-    check(L.nh_intra_rdo_planes_closed(src.data_ptr(), arr, len(sets), int(qp), modes.data_ptr(), lvl.data_ptr(),
-                                       rec.data_ptr(), sse.data_ptr(), work.data_ptr(), st))
-    status = C.c_int(0)
-    check(L.nh_intra_rdo_closed_status(work.data_ptr(), C.byref(status), st))
-    if status.value:
-        raise RuntimeError("intra_rdo_closed: the wavefront stalled (device status word set)")
+    arr = _set_array(sets)
+    _closed_call(what, int(L.nh_intra_rdo_closed_workspace_bytes(arr, len(sets))), src.device, stream,
+                 lambda work, st: L.nh_intra_rdo_planes_closed(src.data_ptr(), arr, len(sets), int(qp), modes.data_ptr(),
+                                                               lvl.data_ptr(), rec.data_ptr(), sse.data_ptr(), work, st))
     return modes[:nmodes], lvl, rec, sse[:nplanes]
 
 
@@ -416,67 +438,15 @@ def intra_rdo_closed_n(src, sets: Sequence[PlaneSet], block_size: int, qp: int =
     outside full blocks), sse int64 per plane).  A bad block size, QP outside
     0..51 or ``use_dst`` with N != 4 raises ValueError; a stalled wavefront raises
     RuntimeError.  N = 8 runs the ``intra_rdo_closed`` kernels."""
-    torch = _torch()
-    _need(src, torch.int16, "intra_rdo_closed_n(src)")
-    n = int(block_size)
-    if n not in (4, 8, 16, 32):
-        raise ValueError(f"intra_rdo_closed_n: block_size must be 4, 8, 16 or 32, got {block_size}")
-    sets_fit(sets, src.numel(), "intra_rdo_closed_n")
-    nmodes = sum((s.width // n) * (s.height // n) * s.planes_per_group * s.num_groups for s in sets)
-    nplanes = sum(s.planes_per_group * s.num_groups for s in sets)
-    dev = src.device
-    if lvl is None:
-        lvl = torch.zeros(src.shape, dtype=torch.int32, device=dev)
-    if rec is None:
-        rec = torch.zeros(src.shape, dtype=torch.int16, device=dev)
-    _need(lvl, torch.int32, "intra_rdo_closed_n(lvl)")
-    _need(rec, torch.int16, "intra_rdo_closed_n(rec)")
-    if lvl.numel() < src.numel() or rec.numel() < src.numel():
-        raise ValueError("intra_rdo_closed_n: lvl / rec smaller than src")
+    what = "intra_rdo_closed_n"
+    n, lvl, rec, modes, sse, nmodes, nplanes = _rdo_prepare(what, src, sets, block_size, lvl, rec)
     L = _lib.load()
-    arr = (PlaneSet * max(1, len(sets)))(*sets)
-    wb = int(L.nh_intra_rdo_closed_n_workspace_bytes(arr, len(sets), n))
-    if wb < 0:
-        raise ValueError("intra_rdo_closed_n: bad argument: " + L.nh_last_error().decode(errors="replace"))
-    modes = torch.zeros(max(1, nmodes), dtype=torch.uint8, device=dev)
-    sse = torch.zeros(max(1, nplanes), dtype=torch.int64, device=dev)
-    work = torch.empty(max(2, (wb + 3) // 4), dtype=torch.int32, device=dev)
-    st = C.c_void_p(_stream(stream, dev))
-    check(L.nh_intra_rdo_planes_closed_n(src.data_ptr(), arr, len(sets), n, int(bool(use_dst)), int(qp),
-                                         modes.data_ptr(), lvl.data_ptr(), rec.data_ptr(), sse.data_ptr(),
-                                         work.data_ptr(), st), "intra_rdo_closed_n")
-    status = C.c_int(0)
-    check(L.nh_intra_rdo_closed_status(work.data_ptr(), C.byref(status), st))
-    if status.value:
-        raise RuntimeError("intra_rdo_closed_n: the wavefront stalled (device status word set)")
+    arr = _set_array(sets)
+    _closed_call(what, int(L.nh_intra_rdo_closed_n_workspace_bytes(arr, len(sets), n)), src.device, stream,
+                 lambda work, st: L.nh_intra_rdo_planes_closed_n(src.data_ptr(), arr, len(sets), n, int(bool(use_dst)),
+                                                                 int(qp), modes.data_ptr(), lvl.data_ptr(),
+                                                                 rec.data_ptr(), sse.data_ptr(), work, st))
     return modes[:nmodes], lvl, rec, sse[:nplanes]
-
-
-def _rdo_rd_prepare(src, sets: Sequence[PlaneSet], block_size: int, lam: int, lvl, rec, what: str):
-    """Argument checks and default outputs shared by the open and the closed RD form
-    (DESIGN.md §3.3b, §3.7b); returns (n, lvl, rec, modes, stats, nmodes, nplanes)."""
-    torch = _torch()
-    _need(src, torch.int16, f"{what}(src)")
-    n = int(block_size)
-    if n not in (4, 8, 16, 32):
-        raise ValueError(f"{what}: block_size must be 4, 8, 16 or 32, got {block_size}")
-    if not 0 <= int(lam) <= 2 ** 31 - 1:
-        raise ValueError(f"{what}: lam (lambda) must be in 0..2^31-1")
-    sets_fit(sets, src.numel(), what)
-    nmodes = sum((s.width // n) * (s.height // n) * s.planes_per_group * s.num_groups for s in sets)
-    nplanes = sum(s.planes_per_group * s.num_groups for s in sets)
-    dev = src.device
-    if lvl is None:
-        lvl = torch.zeros(src.shape, dtype=torch.int32, device=dev)
-    if rec is None:
-        rec = torch.zeros(src.shape, dtype=torch.int16, device=dev)
-    _need(lvl, torch.int32, f"{what}(lvl)")
-    _need(rec, torch.int16, f"{what}(rec)")
-    if lvl.numel() < src.numel() or rec.numel() < src.numel():
-        raise ValueError(f"{what}: lvl / rec smaller than src")
-    modes = torch.zeros(max(1, nmodes), dtype=torch.uint8, device=dev)
-    stats = torch.empty((max(1, nplanes), 3), dtype=torch.int64, device=dev)   # overwritten by the call
-    return n, lvl, rec, modes, stats, nmodes, nplanes
 
 
 def intra_rdo_rd_planes_n(src, sets: Sequence[PlaneSet], block_size: int, qp: int = 32, lam: int = 0,
@@ -493,11 +463,10 @@ def intra_rdo_rd_planes_n(src, sets: Sequence[PlaneSet], block_size: int, qp: in
     arguments raise ValueError (a QP outside 0..51 is not clamped).  N = 8 runs the
     N-lane chains, not the packed ``intra_rdo_planes`` kernels."""
     what = "intra_rdo_rd_planes_n"
-    n, lvl, rec, modes, stats, nmodes, nplanes = _rdo_rd_prepare(src, sets, block_size, lam, lvl, rec, what)
-    arr = (PlaneSet * max(1, len(sets)))(*sets)
-    check(_lib.load().nh_intra_rdo_rd_planes_n(src.data_ptr(), arr, len(sets), n, int(bool(use_dst)), int(qp), int(lam),
-                                               modes.data_ptr(), lvl.data_ptr(), rec.data_ptr(), stats.data_ptr(),
-                                               C.c_void_p(_stream(stream, src.device))), what)
+    n, lvl, rec, modes, stats, nmodes, nplanes = _rdo_rd_prepare(what, src, sets, block_size, lam, lvl, rec)
+    check(_lib.load().nh_intra_rdo_rd_planes_n(src.data_ptr(), _set_array(sets), len(sets), n, int(bool(use_dst)),
+                                               int(qp), int(lam), modes.data_ptr(), lvl.data_ptr(), rec.data_ptr(),
+                                               stats.data_ptr(), C.c_void_p(_stream(stream, src.device))), what)
     return modes[:nmodes], lvl, rec, stats[:nplanes]
 
 
@@ -506,23 +475,8 @@ def intra_rdo_rd_plane_n(src2d, block_size: int, qp: int = 32, lam: int = 0, use
     """``intra_rdo_rd_planes_n`` on one int16 plane (H, W) whose rows are ``pitch``
     (default W) samples apart: (modes u8 (H/N, W/N), levels int32 (H, W), recon int16
     (H, W), stats int64 (1, 3))."""
-    torch = _torch()
-    _need(src2d, torch.int16, "intra_rdo_rd_plane_n")
-    h, w = src2d.shape
-    p = int(pitch or w)
-    if p != w:   # rows of the (H, W) tensor re-spaced: run on a pitched copy, return (H, W) views
-        if p < w:
-            raise ValueError("intra_rdo_rd_plane_n: pitch < width")
-        buf = torch.zeros((h, p), dtype=torch.int16, device=src2d.device)
-        buf[:, :w] = src2d
-        modes, lvl, rec, stats = intra_rdo_rd_planes_n(buf, [plane_set(0, w, h, p)], block_size, qp, lam, use_dst,
-                                                       stream=stream)
-        lvl, rec = lvl[:, :w], rec[:, :w]
-    else:
-        modes, lvl, rec, stats = intra_rdo_rd_planes_n(src2d, [plane_set(0, w, h, w)], block_size, qp, lam, use_dst,
-                                                       stream=stream)
-    n = int(block_size)
-    return modes.reshape(h // n, w // n), lvl, rec, stats
+    return _rdo_one_plane("intra_rdo_rd_plane_n", intra_rdo_rd_planes_n, src2d, block_size, pitch, qp, lam, use_dst,
+                          stream=stream)
 
 
 def intra_rdo_rd_closed_n(src, sets: Sequence[PlaneSet], block_size: int, qp: int = 32, lam: int = 0,
@@ -537,24 +491,30 @@ def intra_rdo_rd_closed_n(src, sets: Sequence[PlaneSet], block_size: int, qp: in
     sum D, sum R, overwritten).  Bad arguments raise ValueError; a stalled wavefront
     raises RuntimeError."""
     what = "intra_rdo_rd_closed_n"
-    n, lvl, rec, modes, stats, nmodes, nplanes = _rdo_rd_prepare(src, sets, block_size, lam, lvl, rec, what)
-    torch = _torch()
-    dev = src.device
+    n, lvl, rec, modes, stats, nmodes, nplanes = _rdo_rd_prepare(what, src, sets, block_size, lam, lvl, rec)
     L = _lib.load()
-    arr = (PlaneSet * max(1, len(sets)))(*sets)
-    wb = int(L.nh_intra_rdo_rd_closed_n_workspace_bytes(arr, len(sets), n))
-    if wb < 0:
-        raise ValueError(f"{what}: bad argument: " + L.nh_last_error().decode(errors="replace"))
-    work = torch.empty(max(2, (wb + 7) // 8 * 2), dtype=torch.int32, device=dev)
-    st = C.c_void_p(_stream(stream, dev))
-    check(L.nh_intra_rdo_rd_planes_closed_n(src.data_ptr(), arr, len(sets), n, int(bool(use_dst)), int(qp), int(lam),
-                                            modes.data_ptr(), lvl.data_ptr(), rec.data_ptr(), stats.data_ptr(),
-                                            work.data_ptr(), st), what)
-    status = C.c_int(0)
-    check(L.nh_intra_rdo_closed_status(work.data_ptr(), C.byref(status), st))
-    if status.value:
-        raise RuntimeError(f"{what}: the wavefront stalled (device status word set)")
+    arr = _set_array(sets)
+    _closed_call(what, int(L.nh_intra_rdo_rd_closed_n_workspace_bytes(arr, len(sets), n)), src.device, stream,
+                 lambda work, st: L.nh_intra_rdo_rd_planes_closed_n(src.data_ptr(), arr, len(sets), n,
+                                                                    int(bool(use_dst)), int(qp), int(lam),
+                                                                    modes.data_ptr(), lvl.data_ptr(), rec.data_ptr(),
+                                                                    stats.data_ptr(), work, st))
     return modes[:nmodes], lvl, rec, stats[:nplanes]
+
+
+def _dequant_need(what: str, lvl, out):
+    """The checks of a stage-R call's level tensor (int16 or int32) and of its int16 ``out``,
+    zero-filled in ``lvl``'s shape by default; returns ``out``."""
+    torch = _torch()
+    if not isinstance(lvl, torch.Tensor) or lvl.dtype not in (torch.int16, torch.int32):
+        raise TypeError(f"{what}(lvl): expected an int16 or int32 CUDA/HIP torch tensor")
+    _need(lvl, lvl.dtype, f"{what}(lvl)")
+    if out is None:
+        out = torch.zeros(lvl.shape, dtype=torch.int16, device=lvl.device)
+    _need(out, torch.int16, f"{what}(out)")
+    if out.device != lvl.device:
+        raise ValueError(f"{what}: out and lvl on different devices")
+    return out
 
 
 def dequant_inv8x8(lvl, sets: Sequence[PlaneSet], qp: int = 32, out=None, stream=None):
@@ -564,18 +524,48 @@ def dequant_inv8x8(lvl, sets: Sequence[PlaneSet], qp: int = 32, out=None, stream
     ``lvl``; exact for every level value of the dtype.  The residual lands at the
     same raster positions of ``out`` (int16, same shape); samples outside full
     blocks are left as they are.  Any pitch >= width and any base."""
-    torch = _torch()
-    if not isinstance(lvl, torch.Tensor) or lvl.dtype not in (torch.int16, torch.int32):
-        raise TypeError("dequant_inv8x8(lvl): expected an int16 or int32 CUDA/HIP torch tensor")
-    _need(lvl, lvl.dtype, "dequant_inv8x8(lvl)")
-    if out is None:
-        out = torch.zeros(lvl.shape, dtype=torch.int16, device=lvl.device)
-    _need(out, torch.int16, "dequant_inv8x8(out)")
+    out = _dequant_need("dequant_inv8x8", lvl, out)
     sets_fit(sets, min(lvl.numel(), out.numel()), "dequant_inv8x8")
-    arr = (PlaneSet * len(sets))(*sets)
-    check(_lib.load().nh_dequant_inv8x8_planes(lvl.data_ptr(), lvl.element_size(), out.data_ptr(), arr, len(sets),
-                                               int(qp), C.c_void_p(_stream(stream, lvl.device))), "dequant_inv8x8")
+    check(_lib.load().nh_dequant_inv8x8_planes(lvl.data_ptr(), lvl.element_size(), out.data_ptr(), _set_array(sets),
+                                               len(sets), int(qp), C.c_void_p(_stream(stream, lvl.device))),
+          "dequant_inv8x8")
     return out
+
+
+def _decode_closed(what: str, modes, lvl, sets: Sequence[PlaneSet], block_size: int, use_dst, qp: int, rec, stream):
+    """``intra_decode_closed_n``; ``use_dst`` None: ``intra_decode_closed``, on the 8x8 entry points."""
+    torch = _torch()
+    _need(lvl, torch.int32, f"{what}(lvl)")
+    _need(modes, torch.uint8, f"{what}(modes)")
+    if modes.device != lvl.device:
+        raise ValueError(f"{what}: modes and lvl on different devices")
+    n = int(block_size)
+    if n not in (4, 8, 16, 32):
+        raise ValueError(f"{what}: block_size must be 4, 8, 16 or 32, got {block_size}")
+    sets_fit(sets, lvl.numel(), what)
+    nmodes = _set_counts(sets, n)[0]
+    if modes.numel() < nmodes:
+        raise ValueError(f"{what}: {modes.numel()} modes for {nmodes} blocks")
+    if rec is None:
+        rec = torch.zeros(lvl.shape, dtype=torch.int16, device=lvl.device)
+    _need(rec, torch.int16, f"{what}(rec)")
+    if rec.device != lvl.device:
+        raise ValueError(f"{what}: rec and lvl on different devices")
+    if rec.numel() < lvl.numel():
+        raise ValueError(f"{what}: rec smaller than lvl")
+    if nmodes == 0:   # no full block anywhere: the device still zeroes rec, but reads no mode
+        modes = torch.zeros(1, dtype=torch.uint8, device=lvl.device)
+    L = _lib.load()
+    arr = _set_array(sets)
+    if use_dst is None:
+        wb, entry, form = L.nh_intra_decode_closed_workspace_bytes(arr, len(sets)), L.nh_intra_decode_planes_closed, ()
+    else:
+        wb, entry = L.nh_intra_decode_closed_n_workspace_bytes(arr, len(sets), n), L.nh_intra_decode_planes_closed_n
+        form = (n, int(bool(use_dst)))
+    _closed_call(what, int(wb), lvl.device, stream,
+                 lambda work, st: entry(modes.data_ptr(), lvl.data_ptr(), arr, len(sets), *form, int(qp), rec.data_ptr(),
+                                        work, st), "a mode above 34 in the mode map")
+    return rec
 
 
 def intra_decode_closed(modes, lvl, sets: Sequence[PlaneSet], qp: int = 32, rec=None, stream=None):
@@ -584,40 +574,7 @@ def intra_decode_closed(modes, lvl, sets: Sequence[PlaneSet], qp: int = 32, rec=
     ``qp``, rebuild its reconstruction -- stage R, then one prediction per block
     in closed loop on the row wavefront.  Returns recon int16 (source layout, 0
     outside full blocks).  A mode above 34 raises ValueError."""
-    torch = _torch()
-    _need(lvl, torch.int32, "intra_decode_closed(lvl)")
-    _need(modes, torch.uint8, "intra_decode_closed(modes)")
-    if modes.device != lvl.device:
-        raise ValueError("intra_decode_closed: modes and lvl on different devices")
-    sets_fit(sets, lvl.numel(), "intra_decode_closed")
-    L = _lib.load()
-    arr = (PlaneSet * len(sets))(*sets)
-    wb = int(L.nh_intra_decode_closed_workspace_bytes(arr, len(sets)))
-    if wb < 0:
-        raise ValueError("intra_decode_closed: bad plane sets")
-    nmodes = sum((s.width // 8) * (s.height // 8) * s.planes_per_group * s.num_groups for s in sets)
-    if modes.numel() < nmodes:
-        raise ValueError(f"intra_decode_closed: {modes.numel()} modes for {nmodes} blocks")
-    if rec is None:
-        rec = torch.zeros(lvl.shape, dtype=torch.int16, device=lvl.device)
-    _need(rec, torch.int16, "intra_decode_closed(rec)")
-    if rec.device != lvl.device:
-        raise ValueError("intra_decode_closed: rec and lvl on different devices")
-    if rec.numel() < lvl.numel():
-        raise ValueError("intra_decode_closed: rec smaller than lvl")
-    if nmodes == 0:   # no full block anywhere: the device still zeroes rec, but reads no mode
-        modes = torch.zeros(1, dtype=torch.uint8, device=lvl.device)
-    work = torch.empty((wb + 3) // 4, dtype=torch.int32, device=lvl.device)
-    st = C.c_void_p(_stream(stream, lvl.device))
-    check(L.nh_intra_decode_planes_closed(modes.data_ptr(), lvl.data_ptr(), arr, len(sets), int(qp), rec.data_ptr(),
-                                          work.data_ptr(), st), "intra_decode_closed")
-    status = C.c_int(0)
-    check(L.nh_intra_rdo_closed_status(work.data_ptr(), C.byref(status), st))
-    if status.value == 2:
-        raise ValueError("intra_decode_closed: a mode above 34 in the mode map")
-    if status.value:
-        raise RuntimeError("intra_decode_closed: the wavefront stalled (device status word set)")
-    return rec
+    return _decode_closed("intra_decode_closed", modes, lvl, sets, 8, None, qp, rec, stream)
 
 
 def dequant_inv_n(lvl, sets: Sequence[PlaneSet], block_size: int, qp: int = 32, use_dst: bool = False, out=None,
@@ -631,19 +588,10 @@ def dequant_inv_n(lvl, sets: Sequence[PlaneSet], block_size: int, qp: int = 32, 
     blocks are left as they are.  Any pitch >= width and any base.  A refusal of
     the library (bad block size, ``use_dst`` with N != 4, bad plane sets) raises
     ValueError with its text."""
-    torch = _torch()
-    if not isinstance(lvl, torch.Tensor) or lvl.dtype not in (torch.int16, torch.int32):
-        raise TypeError("dequant_inv_n(lvl): expected an int16 or int32 CUDA/HIP torch tensor")
-    _need(lvl, lvl.dtype, "dequant_inv_n(lvl)")
-    if out is None:
-        out = torch.zeros(lvl.shape, dtype=torch.int16, device=lvl.device)
-    _need(out, torch.int16, "dequant_inv_n(out)")
-    if out.device != lvl.device:
-        raise ValueError("dequant_inv_n: out and lvl on different devices")
+    out = _dequant_need("dequant_inv_n", lvl, out)
     sets_fit(sets, min(lvl.numel(), out.numel()), "dequant_inv_n")
-    arr = (PlaneSet * max(1, len(sets)))(*sets)
-    check(_lib.load().nh_dequant_inv_planes_n(lvl.data_ptr(), lvl.element_size(), out.data_ptr(), arr, len(sets),
-                                              int(block_size), int(bool(use_dst)), int(qp),
+    check(_lib.load().nh_dequant_inv_planes_n(lvl.data_ptr(), lvl.element_size(), out.data_ptr(), _set_array(sets),
+                                              len(sets), int(block_size), int(bool(use_dst)), int(qp),
                                               C.c_void_p(_stream(stream, lvl.device))), "dequant_inv_n")
     return out
 
@@ -659,41 +607,7 @@ def intra_decode_closed_n(modes, lvl, sets: Sequence[PlaneSet], block_size: int,
     block size, ``use_dst`` with N != 4, bad plane sets) raises ValueError; a
     stalled wavefront raises RuntimeError.  N = 8 runs ``intra_decode_closed``'s
     kernels."""
-    torch = _torch()
-    _need(lvl, torch.int32, "intra_decode_closed_n(lvl)")
-    _need(modes, torch.uint8, "intra_decode_closed_n(modes)")
-    if modes.device != lvl.device:
-        raise ValueError("intra_decode_closed_n: modes and lvl on different devices")
-    sets_fit(sets, lvl.numel(), "intra_decode_closed_n")
-    n = int(block_size)
-    L = _lib.load()
-    arr = (PlaneSet * max(1, len(sets)))(*sets)
-    wb = int(L.nh_intra_decode_closed_n_workspace_bytes(arr, len(sets), n))
-    if wb < 0:
-        raise ValueError("intra_decode_closed_n: bad argument: " + L.nh_last_error().decode(errors="replace"))
-    nmodes = sum((s.width // n) * (s.height // n) * s.planes_per_group * s.num_groups for s in sets)
-    if modes.numel() < nmodes:
-        raise ValueError(f"intra_decode_closed_n: {modes.numel()} modes for {nmodes} blocks")
-    if rec is None:
-        rec = torch.zeros(lvl.shape, dtype=torch.int16, device=lvl.device)
-    _need(rec, torch.int16, "intra_decode_closed_n(rec)")
-    if rec.device != lvl.device:
-        raise ValueError("intra_decode_closed_n: rec and lvl on different devices")
-    if rec.numel() < lvl.numel():
-        raise ValueError("intra_decode_closed_n: rec smaller than lvl")
-    if nmodes == 0:   # no full block anywhere: the device still zeroes rec, but reads no mode
-        modes = torch.zeros(1, dtype=torch.uint8, device=lvl.device)
-    work = torch.empty(max(2, (wb + 3) // 4), dtype=torch.int32, device=lvl.device)
-    st = C.c_void_p(_stream(stream, lvl.device))
-    check(L.nh_intra_decode_planes_closed_n(modes.data_ptr(), lvl.data_ptr(), arr, len(sets), n, int(bool(use_dst)),
-                                            int(qp), rec.data_ptr(), work.data_ptr(), st), "intra_decode_closed_n")
-    status = C.c_int(0)
-    check(L.nh_intra_rdo_closed_status(work.data_ptr(), C.byref(status), st))
-    if status.value == 2:
-        raise ValueError("intra_decode_closed_n: a mode above 34 in the mode map")
-    if status.value:
-        raise RuntimeError("intra_decode_closed_n: the wavefront stalled (device status word set)")
-    return rec
+    return _decode_closed("intra_decode_closed_n", modes, lvl, sets, block_size, bool(use_dst), qp, rec, stream)
 
 
 def intra_rdo_closed_yuv420_stream(src, width: int, height: int, num_frames: int, qp: int = 32,
@@ -775,10 +689,7 @@ def intra_rdo_closed_yuv420_stream(src, width: int, height: int, num_frames: int
         both = works[0][:2].clone()
         for w_ in works[1:]:
             both.bitwise_or_(w_[:2])
-    status = C.c_int(0)
-    check(L.nh_intra_rdo_closed_status(both.data_ptr(), C.byref(status), C.c_void_p(main.cuda_stream)))
-    if status.value:
-        raise RuntimeError("intra_rdo_closed_yuv420_stream: the wavefront stalled (device status word set)")
+    _closed_status(both, int(main.cuda_stream), "intra_rdo_closed_yuv420_stream")
     return modes[:num_frames * (ny + 2 * nc)], lvl, rec, sse[:3 * num_frames]
 
 
@@ -927,13 +838,6 @@ def _tu_closed_launch_on(src, pset, ctb, plane_id, seed, qp, is_luma, lvl, rec, 
     return lvl, rec, tu, work
 
 
-def _tu_closed_status(work, st: int, what: str):
-    status = C.c_int(0)
-    check(_lib.load().nh_intra_rdo_closed_status(work.data_ptr(), C.byref(status), C.c_void_p(st)))
-    if status.value:
-        raise RuntimeError("%s: the device wavefront stalled (status %d)" % (what, status.value))
-
-
 def tu_pipeline_closed(src, pset: PlaneSet, ctb: int, plane_id: int, seed: int, qp: int = 32, is_luma: bool = True,
                        lvl=None, rec=None, tu=None, stream=None):
     """Config 4 in CLOSED loop over every plane of one plane
@@ -947,7 +851,7 @@ def tu_pipeline_closed(src, pset: PlaneSet, ctb: int, plane_id: int, seed: int, 
     strm = stream if stream is not None else torch.cuda.current_stream(src.device)
     st = _stream(strm, src.device)
     lvl, rec, tu, work = _tu_closed_launch(src, pset, ctb, plane_id, seed, qp, is_luma, lvl, rec, tu, strm)
-    _tu_closed_status(work, st, "tu_pipeline_closed")
+    _closed_status(work, st, "tu_pipeline_closed")
     return lvl, rec, tu
 
 
@@ -998,10 +902,10 @@ def tu_pipeline_closed_yuv420(src, luma: PlaneSet, chroma: PlaneSet, seed: int, 
         both = work_y[:1].clone()
         both.view(torch.int32)[1:2].bitwise_or_(work_c[:1].view(torch.int32)[1:2])
     try:
-        _tu_closed_status(both, int(main.cuda_stream), "tu_pipeline_closed_yuv420")
+        _closed_status(both, int(main.cuda_stream), "tu_pipeline_closed_yuv420")
     except RuntimeError:
-        _tu_closed_status(work_y, int(main.cuda_stream), "tu_pipeline_closed_yuv420 (luma)")
-        _tu_closed_status(work_c, int(main.cuda_stream), "tu_pipeline_closed_yuv420 (chroma)")
+        _closed_status(work_y, int(main.cuda_stream), "tu_pipeline_closed_yuv420 (luma)")
+        _closed_status(work_c, int(main.cuda_stream), "tu_pipeline_closed_yuv420 (chroma)")
         raise
     return lvl, rec, tu_luma, tu_chroma
 
@@ -1060,16 +964,8 @@ def dequant_inv_tu(lvl, tu, pset: PlaneSet, ctb: int, is_luma: bool = True, qp: 
     level value of the dtype.  The residual lands at the same positions of ``out``
     (int16).  The map is not validated here (``tu_decode_closed`` does): a bad one
     is memory-safe and gives an unspecified residual."""
-    torch = _torch()
-    if not isinstance(lvl, torch.Tensor) or lvl.dtype not in (torch.int16, torch.int32):
-        raise TypeError("dequant_inv_tu(lvl): expected an int16 or int32 CUDA/HIP torch tensor")
-    _need(lvl, lvl.dtype, "dequant_inv_tu(lvl)")
+    out = _dequant_need("dequant_inv_tu", lvl, out)
     _tu_set_check(pset, ctb, "dequant_inv_tu")
-    if out is None:
-        out = torch.zeros(lvl.shape, dtype=torch.int16, device=lvl.device)
-    _need(out, torch.int16, "dequant_inv_tu(out)")
-    if out.device != lvl.device:
-        raise ValueError("dequant_inv_tu: out and lvl on different devices")
     sets_fit([pset], min(lvl.numel(), out.numel()), "dequant_inv_tu")
     _tu_map_need(tu, pset, lvl.device, "dequant_inv_tu(tu)")
     check(_lib.load().nh_dequant_inv_tu_planes(lvl.data_ptr(), lvl.element_size(), out.data_ptr(), tu.data_ptr(),
@@ -1106,14 +1002,8 @@ def _tu_decode_launch(tu, pm, lvl, pset: PlaneSet, ctb: int, is_luma: bool, qp: 
     return rec, work
 
 
-def _tu_decode_status(work, st: int, what: str):
-    status = C.c_int(0)
-    check(_lib.load().nh_intra_rdo_closed_status(work.data_ptr(), C.byref(status), C.c_void_p(st)))
-    if status.value == 2:
-        raise ValueError(f"{what}: bad map (tu is no partition into aligned squares of 4..ctb samples inside "
-                         "the plane, or a pm value above 1; status 2)")
-    if status.value:
-        raise RuntimeError("%s: the device wavefront stalled (status %d)" % (what, status.value))
+_TU_BAD_MAP = ("bad map (tu is no partition into aligned squares of 4..ctb samples inside the plane, or a pm value "
+               "above 1; status 2)")
 
 
 def tu_decode_closed(tu, pm, lvl, pset: PlaneSet, ctb: int, qp: int = 32, is_luma: bool = True, rec=None,
@@ -1132,7 +1022,7 @@ def tu_decode_closed(tu, pm, lvl, pset: PlaneSet, ctb: int, qp: int = 32, is_lum
     strm = stream if stream is not None else torch.cuda.current_stream(lvl.device)
     st = _stream(strm, lvl.device)
     rec, work = _tu_decode_launch(tu, pm, lvl, pset, ctb, is_luma, qp, rec, strm)
-    _tu_decode_status(work, st, "tu_decode_closed")
+    _closed_status(work, st, "tu_decode_closed", _TU_BAD_MAP)
     return rec
 
 
@@ -1178,12 +1068,12 @@ def tu_decode_closed_yuv420(tu_luma, pm_luma, tu_chroma, pm_chroma, lvl, luma: P
         both = work_y[:1].clone()
         both.view(torch.int32)[1:2].bitwise_or_(work_c[:1].view(torch.int32)[1:2])
     try:
-        _tu_decode_status(both, int(main.cuda_stream), "tu_decode_closed_yuv420")
+        _closed_status(both, int(main.cuda_stream), "tu_decode_closed_yuv420", _TU_BAD_MAP)
     except (ValueError, RuntimeError):   # name the set; a bad map (status 2) goes before a stall (status 1)
         errs = []
         for work, name in ((work_y, "luma"), (work_c, "chroma")):
             try:
-                _tu_decode_status(work, int(main.cuda_stream), "tu_decode_closed_yuv420 (%s)" % name)
+                _closed_status(work, int(main.cuda_stream), "tu_decode_closed_yuv420 (%s)" % name, _TU_BAD_MAP)
             except (ValueError, RuntimeError) as e:
                 errs.append(e)
         for e in sorted(errs, key=lambda e: not isinstance(e, ValueError)):
@@ -1368,10 +1258,10 @@ def tu_pipeline_closed_yuv420_stream(src, width: int, height: int, num_frames: i
         for w_ in works[1:]:
             both.view(torch.int32)[1:2].bitwise_or_(w_[:1].view(torch.int32)[1:2])
     try:
-        _tu_closed_status(both, int(main.cuda_stream), "tu_pipeline_closed_yuv420_stream")
+        _closed_status(both, int(main.cuda_stream), "tu_pipeline_closed_yuv420_stream")
     except RuntimeError:
         for k, w_ in enumerate(works):
-            _tu_closed_status(w_, int(main.cuda_stream),
+            _closed_status(w_, int(main.cuda_stream),
                               f"tu_pipeline_closed_yuv420_stream (batch {k // 2}, {'chroma' if k % 2 else 'luma'})")
         raise
     return lvl, rec, tu_luma, tu_chroma
@@ -1408,7 +1298,7 @@ def tc32_planes(src, sets, qp: int = 32, variant: int = 1, lvl=None, rec=None, s
     _need(rec, torch.int16, "tc32_planes(rec)")
     if lvl.numel() < src.numel() or rec.numel() < src.numel():
         raise ValueError("tc32_planes: lvl / rec smaller than src")
-    arr = (PlaneSet * len(sets))(*sets)
+    arr = _set_array(sets)
     check(_lib.load().nh_tc32_planes(src.data_ptr(), arr, len(sets), int(qp), lvl.data_ptr(), rec.data_ptr(),
                                      int(variant), C.c_void_p(_stream(stream, src.device))), "tc32_planes")
     return lvl, rec
@@ -1440,7 +1330,7 @@ def tc32_planes_compact(src, sets, qp: int = 32, level_dtype=None, lvl=None, rec
     _need(spill, torch.int32, "tc32_planes_compact(spill)")
     if min(lvl.numel(), rec.numel(), spill.numel()) < src.numel():
         raise ValueError("tc32_planes_compact: lvl / rec / spill smaller than src")
-    arr = (PlaneSet * len(sets))(*sets)
+    arr = _set_array(sets)
     check(_lib.load().nh_tc32_planes_compact(src.data_ptr(), arr, len(sets), int(qp), lvl.data_ptr(),
                                              lvl.element_size(), spill.data_ptr(), rec.data_ptr(),
                                              C.c_void_p(_stream(stream, src.device))), "tc32_planes_compact")
@@ -1460,7 +1350,7 @@ def tc32_levels_widen(lvl, spill, sets, out=None, stream=None):
         out = torch.zeros(lvl.shape, dtype=torch.int32, device=lvl.device)
     _need(out, torch.int32, "tc32_levels_widen(out)")
     sets_fit(sets, min(lvl.numel(), spill.numel(), out.numel()), "tc32_levels_widen")
-    arr = (PlaneSet * len(sets))(*sets)
+    arr = _set_array(sets)
     check(_lib.load().nh_tc32_levels_widen(lvl.data_ptr(), lvl.element_size(), spill.data_ptr(), arr, len(sets),
                                            out.data_ptr(), C.c_void_p(_stream(stream, lvl.device))),
           "tc32_levels_widen")
@@ -1546,7 +1436,7 @@ def encode_intra_planes(src, sets: Sequence[PlaneSet], block_sizes: Sequence[int
             _need(t, dt, f"encode_intra_planes({nm})")
             if t.numel() < src.numel():
                 raise ValueError(f"encode_intra_planes: {nm} smaller than src")
-    arr = (PlaneSet * len(sets))(*sets)
+    arr = _set_array(sets)
     bsz = (C.c_int32 * len(sets))(*[int(b) for b in block_sizes])
     wide = src.dtype == torch.int16 and any(int(b) & (int(b) - 1) or int(b) < 4 or int(b) > 64 for b in block_sizes)
     status = torch.zeros(1, dtype=torch.int32, device=src.device) if wide else None

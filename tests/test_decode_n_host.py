@@ -148,6 +148,26 @@ def test_refusals_precede_any_device_call():
         assert b"null" in L.nh_last_error()
 
 
+def test_a_qp_outside_0_51_is_not_refused():
+    """A decoder clamps QP: with QP 52 or -1 a call whose only fault comes later in the checks -- a level
+    size of 3 bytes, a misaligned workspace -- is refused for that fault, not for the QP."""
+    from nano_hevc import _lib
+    from nano_hevc._lib import PlaneSet
+    L = _lib.load()
+    fake, odd = C.c_void_p(1 << 20), C.c_void_p((1 << 20) + 4)
+    ok = PlaneSet(0, 0, 0, 64, 64, 64, 1, 1, 0)
+    for qp in (52, -1):
+        for n in (4, 8, 16, 32):
+            assert L.nh_dequant_inv_planes_n(fake, 3, fake, C.byref(ok), 1, n, 0, qp, None) == _lib.NH_EARG, (n, qp)
+            err = L.nh_last_error()
+            assert b"lvl_bytes" in err and b"qp" not in err, err
+        for n in (4, 16, 32):              # N = 8 is forwarded after the argument checks
+            assert L.nh_intra_decode_planes_closed_n(fake, fake, C.byref(ok), 1, n, 0, qp, fake, odd,
+                                                     None) == _lib.NH_EARG, (n, qp)
+            err = L.nh_last_error()
+            assert b"8-byte" in err and b"qp" not in err, err
+
+
 def test_workspace_size_is_the_encoders():
     from nano_hevc import _lib
     from nano_hevc._lib import PlaneSet

@@ -90,6 +90,25 @@ def test_refusals_precede_any_device_call():
     assert L.nh_intra_rdo_planes_n(None, C.byref(ok), 1, 16, 0, 30, fake, fake, fake, fake, None) == _lib.NH_EARG
 
 
+def test_the_sse_pointer_is_optional_in_the_open_loop_only():
+    """nh_intra_rdo_planes_n takes d_sse = NULL: with QP 52 besides, the refusal is the QP's.  The closed
+    loop needs its sums: the same call on nh_intra_rdo_planes_closed_n is refused for the null pointer,
+    which comes first."""
+    from nano_hevc import _lib
+    from nano_hevc._lib import PlaneSet
+    L = _lib.load()
+    fake = C.c_void_p(1 << 20)
+    ok = PlaneSet(0, 0, 0, 64, 64, 64, 1, 1, 0)
+    for n in (4, 8, 16, 32):
+        assert L.nh_intra_rdo_planes_n(fake, C.byref(ok), 1, n, 0, 52, fake, fake, fake, None, None) == _lib.NH_EARG, n
+        err = L.nh_last_error()
+        assert b"nh_intra_rdo_planes_n:" in err and b"qp" in err and b"null" not in err, err
+        assert L.nh_intra_rdo_planes_closed_n(fake, C.byref(ok), 1, n, 0, 52, fake, fake, fake, None, fake,
+                                              None) == _lib.NH_EARG, n
+        err = L.nh_last_error()
+        assert b"nh_intra_rdo_planes_closed_n:" in err and b"null" in err, err
+
+
 def test_sets_without_a_full_block_launch_nothing():
     """A set smaller than N in one dimension (or without planes) holds no block: the call
     returns NH_OK without touching the device (fake pointers again)."""

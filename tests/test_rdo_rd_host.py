@@ -181,6 +181,10 @@ def test_refusals_precede_any_device_call(which):
         ptrs[i] = None
         refused(call(ptrs=ptrs), b"null")
     refused(call(sets=None), b"null")
+    ptrs = [fake] * nptr
+    ptrs[4] = None                     # the null stats pointer is refused before the QP
+    for n in (4, 8, 16, 32):
+        refused(call(n=n, qp=52, ptrs=ptrs), b"null")
     odd = [fake] * nptr
     odd[4] = C.c_void_p((1 << 20) + 4)
     refused(call(ptrs=odd), b"d_stats")
@@ -212,6 +216,7 @@ def test_workspace_size():
     for n in (4, 8, 16, 32):
         # per plane (w + 1) / 2 + N line words of 8 bytes, after the ticket and the status word: at N = 8 too
         assert size(sets, 2, n) == 8 + 8 * (3 * (35 + n) + 2 * (20 + n)), n
+    assert size(sets, 2, 8) != L.nh_intra_rdo_closed_workspace_bytes(sets, 2) > 0   # N = 8 is not forwarded
     assert size(None, 1, 16) < 0 and b"null" in L.nh_last_error()
     for n in (0, 12, 64):
         assert size(sets, 2, n) < 0 and b"block_size" in L.nh_last_error(), n

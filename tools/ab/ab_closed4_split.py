@@ -113,7 +113,7 @@ def main():
                 j.record(s_)
                 main.wait_event(j)
         for w_ in works:
-            gpu._tu_closed_status(w_, int(main.cuda_stream), "pipe")
+            gpu._closed_status(w_, int(main.cuda_stream), "pipe")
 
     forms = {
         "luma": lambda: gpu.tu_pipeline_closed(stream, sy, 32, 0, 1234, args.qp, True, lvl=lv, rec=rc, tu=tuy),
